@@ -9,7 +9,12 @@ synthetic LJSpeech-shaped batch per GPU: parse_batch -> forward -> Tacotron2Loss
 not already running under torch.distributed.run) -> clip_grad_norm_ -> Adam.  Inputs are resident
 in HBM before the timed region.  Metric: VALID mel frames per second, whole job.
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line (with the timed loop's audit and the build hash).
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy (float32, seeded inputs: two
+builds can be compared output for output).  Everything below is measured only with `--full`; `--record FILE` then also
+writes the verbose record (every leg, with its prose) as JSON.
+
+Extra objects in the JSON line with --full:
   roofline      the DOMINANT kernel of the step = whichever of the four kernels of a decoder time step (attention
                 backward + folded cells, fused LSTM pair, BPTT dgrad pair, attention forward) has the largest total
                 duration, each measured live in four extra untimed steps by event pairs that the dispatch itself stamps
@@ -65,7 +70,40 @@ def parse_args():
                          "accurate-fast mode (f32-class split-bf16 products everywhere the fp32 mode used the exact-f32 MFMA)")
     ap.add_argument("--decoder-streams", type=int, default=1, choices=(1, 2),
                     help="1: single stream, fused launches (default); 2: decoder-LSTM chain on a side stream")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: roofline, fp32 / bf16x3 modes, optimiser A/B, CPU baseline + "
+                         "parity check, inference (each still subject to its --no-* / --cpu-sample switch)")
+    ap.add_argument("--record", metavar="FILE", help="with --full: write the verbose record of the run as JSON to FILE")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (loss, model outputs, a seeded sample of the updated "
+                         "parameters and of the gradients) as DIR/<name>.npy, float32, at most 60 MB in all")
     return ap.parse_args()
+
+
+DUMP_MAX_ELEMENTS = 2500000          # per array (10 MB of float32): six sampled arrays and the loss stay below 64 MB
+
+
+def dump_outputs(dirname, loss, y_pred, model):
+    """The arrays a caller of the timed training step receives: the loss, the four model outputs (mel, postnet mel, gate,
+    alignments) and the model after the step (parameters and their gradients, each flattened in named_parameters order).
+    An array larger than DUMP_MAX_ELEMENTS is replaced by a fixed sample: the same seeded, sorted flat indices every run."""
+    import numpy as np
+
+    def sample(t):
+        t = t.detach().float().cpu()
+        if t.numel() <= DUMP_MAX_ELEMENTS:
+            return t
+        idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(1234))[:DUMP_MAX_ELEMENTS].sort().values
+        return t.reshape(-1)[idx]
+
+    params = [p for _, p in model.named_parameters()]
+    arrays = {"loss": loss.reshape(()),
+              "mel_outputs": y_pred[0], "mel_outputs_postnet": y_pred[1], "gate_outputs": y_pred[2], "alignments": y_pred[3],
+              "parameters": torch.cat([p.detach().reshape(-1) for p in params]),
+              "gradients": torch.cat([p.grad.detach().reshape(-1) for p in params])}
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), sample(t).numpy().astype(np.float32))
 
 
 def kernel_source_sha1():
@@ -302,7 +340,7 @@ def _r(x, n=4):
 
 def compact_line(out):
     """The stdout line: every contract key, `roofline` (dominant kernel + the four chain kernels + whole step) and
-    `cpu_baseline` in full meaning but without prose and 17-digit floats; everything else lives in gpurun_out/bench_full.json."""
+    `cpu_baseline` in full meaning but without prose and 17-digit floats; everything else lives in the --record file."""
     o = {k: _r(out[k], 3) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                     "scaling", "vs_baseline", "dtype", "data") if k in out}
     o["config"] = {"workload": "BASELINE configs[1]: LJSpeech default hparams, batch_size=%d/GPU, synthetic LJSpeech-shaped batches, "
@@ -454,8 +492,9 @@ def main():
     torch.cuda.synchronize()
 
     ITEM_EACH_STEP = os.environ.get('T2AMD_BENCH_ITEM', '0') == '1'
+    last_outputs = []                   # the model outputs of the last timed step, kept only for --dump-outputs
 
-    def step(batch):
+    def step(batch, keep_outputs=False):
         model.zero_grad()
         x, y = model.parse_batch(batch)
         y_pred = model(x)
@@ -468,6 +507,8 @@ def main():
         else:
             torch.nn.utils.clip_grad_norm_(model.parameters(), hp.grad_clip_thresh)
             optimizer.step()
+        if keep_outputs:
+            last_outputs[:] = y_pred
         return loss
 
     from tacotron2_amd import engine as _engine
@@ -514,6 +555,7 @@ def main():
                 gc_full.append(round(1e3 * (time.perf_counter() - _t[0]), 2))
         if world > 1:
             dist.barrier()
+        last_outputs.clear()
         torch.cuda.synchronize()
         gc.callbacks.append(_gc_cb)
         mem0 = torch.cuda.memory_stats(dev)
@@ -521,7 +563,7 @@ def main():
         t0 = time.perf_counter()
         loss = None
         for i in range(args.warmup, n_iter):
-            loss = step(batches[i])
+            loss = step(batches[i], keep_outputs=bool(args.dump_outputs) and i == n_iter - 1)
             step_events[i - args.warmup + 1].record()
         torch.cuda.synchronize()
         if world > 1:
@@ -581,6 +623,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         elapsed, timed_frames = tmax[0].item(), t[1].item()
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last_outputs, model)
+    last_outputs.clear()
     # What a SCALE record needs to be checkable from the line alone: the backend that ran, the world it saw,
     # one device identity per rank (N ranks on N DISTINCT GPUs), the decoder-loop forms every rank ended on and every rank's
     # give-up / demotion counters -- "RCCL saw N ranks on N GPUs and nobody fell back to the chain" can be read off it.
@@ -602,11 +647,11 @@ def main():
 
     # ---- roofline: the four kernels of a decoder time step, each timed live in its own extra untimed step ------
     roofline = None
-    if not args.no_roofline and rank != 0:
+    if args.full and not args.no_roofline and rank != 0:
         for _ in range(4):                # the gradient exchange is collective: every rank runs the extra steps
             step(batches[-1])
         torch.cuda.synchronize()
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         To = batches[-1][2].shape[2]
         fused = args.decoder_streams == 1
         B, Ha, Hd, E = args.batch_size, hp.attention_rnn_dim, hp.decoder_rnn_dim, hp.encoder_embedding_dim
@@ -769,7 +814,7 @@ def main():
         model.precision = args.precision
         return {"value": fr / dt, "unit": "valid mel-frames/s", "ms_per_step": 1e3 * dt / k32, "steps": k32, "note": note}
 
-    if args.precision == "bf16" and not args.no_fp32_leg:
+    if args.full and args.precision == "bf16" and not args.no_fp32_leg:
         fp32_leg = extra_leg("fp32", "same workload with model.precision='fp32' (exact-f32 MFMA forward: the mode the 1e-4 / "
                                      "bit-exact-stop parity tests run in)")
         x3_leg = extra_leg("bf16x3", "same workload with model.precision='bf16x3' (round 6, the accurate-fast mode: the fp32 mode with "
@@ -778,7 +823,7 @@ def main():
                                      "tolerances in tests/test_parity_gpu.py and tests/test_zz5_fullsize_parity_gpu.py)")
     # ---- optimiser A/B: the same step with the other clip + Adam implementation (fresh optimiser state) ----------
     optimizer_ab = None
-    if world == 1 and not args.no_optimizer_ab:
+    if args.full and world == 1 and not args.no_optimizer_ab:
         from tacotron2_amd.optim import FusedAdam
         res = {}
         for which in ("torch", "fused"):
@@ -852,26 +897,27 @@ def main():
                               "(tests/test_zz5_fullsize_parity_gpu.py, profiles/r03_parity_fullsize_train_B64_*.json)")
         if optimizer_ab:
             out["optimizer_ab"] = optimizer_ab
-        if args.gpus == 1 and args.cpu_sample > 0:
+        if args.full and args.gpus == 1 and args.cpu_sample > 0:
             out["cpu_baseline"], ctx = cpu_baseline(args.cpu_sample, 1234, args.cpu_threads)
             try:
                 parity = parity_check(ctx, dev)
             except Exception as e:                 # noqa: BLE001
                 parity = {"ok": False, "error": "%s: %s" % (type(e).__name__, e)}
             out["parity_check"] = parity
-        if args.gpus == 1 and not args.no_inference:
+        if args.full and args.gpus == 1 and not args.no_inference:
             try:                                   # never let the secondary metric take the headline line down
                 out["inference"] = inference_leg(dev)
             except Exception as e:                 # noqa: BLE001
                 out["inference"] = {"error": "%s: %s" % (type(e).__name__, e)}
         # the verbose record goes to a side file; the ONE line on stdout stays compact (the driver keeps a bounded tail of
         # stdout: round 2's 5.7 KB line was parsed, a 10 KB one need not be)
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_full.json"), "w") as fh:
-                json.dump(out, fh, indent=1)
-        except OSError:
-            pass
+        if args.full and args.record:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(args.record)), exist_ok=True)
+                with open(args.record, "w") as fh:
+                    json.dump(out, fh, indent=1)
+            except OSError:
+                pass
         print(json.dumps(compact_line(out)), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -144,6 +144,7 @@ def run_train_case(name, case, ref_model, ref_loss):
               grad_small={k: v for k, v in ref_grads.items() if v.numel() <= 4096},
               buffers={k: v for k, v in ref_bufs.items()})
     torch.save(fx, os.path.join(gu.GOLDEN_DIR, name + ".pt"))
+    return fx, ref_grads
 
 
 def pick_threshold(sig, lo_frac=0.25, hi_frac=0.9):

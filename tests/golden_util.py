@@ -77,6 +77,22 @@ def make_train_batch(in_lens, out_lens, n_mel, seed):
     return text, torch.tensor(in_lens), mel, gate, torch.tensor(out_lens)
 
 
+def collate_items(g):
+    """The 60 seeded ragged batches of the collate fixture (tests/golden/make_golden_dropin.py), drawn in a fixed order
+    from generator ``g``: ``[(n_frames_per_step, [(text, mel), ...]), ...]``."""
+    cases = []
+    for _ in range(60):
+        n = int(torch.randint(1, 9, (1,), generator=g))
+        r = int(torch.randint(1, 5, (1,), generator=g))
+        items = []
+        for _ in range(n):
+            ti = int(torch.randint(1, 12, (1,), generator=g))
+            to = int(torch.randint(1, 40, (1,), generator=g))
+            items.append((torch.randint(1, 148, (ti,), generator=g, dtype=torch.int32), torch.randn(80, to, generator=g)))
+        cases.append((r, items))
+    return cases
+
+
 def make_text(in_lens, seed):
     g = torch.Generator().manual_seed(seed + 11)
     B, Ti = len(in_lens), max(in_lens)

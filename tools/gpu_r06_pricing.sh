@@ -4,7 +4,7 @@
 #   item 5 (decoder-LSTM chain off the backward's critical path): the chain without cell_d and the K = 4 Hd dgrad half (NOT legal
 #           arithmetic: T2AMD_BWD_TIMING_NO_D=1), at split-K 2 and 4
 out=gpurun_out; mkdir -p $out
-args="--steps 6 --warmup 2 --cpu-sample 0 --no-fp32-leg --no-inference --no-optimizer-ab"
+args="--full --steps 6 --warmup 2 --cpu-sample 0 --no-fp32-leg --no-inference --no-optimizer-ab"
 pick='import json,sys; d=json.load(sys.stdin); r=d["roofline"]; print(json.dumps({"ms_per_step": d["ms_per_step"], "value": d["value"], "chain": {k: {"avg_launch_us": v["avg_launch_us"], "us_per_time_step": v["us_per_time_step"], "launches": v["launches"]} for k, v in r["chain"].items()}}))'
 echo "{" > $out/r06_e_ceilings.json
 echo "\"B64_product\": $(python bench.py $args 2>/dev/null | python -c "$pick")," >> $out/r06_e_ceilings.json
