@@ -908,6 +908,47 @@ int t2amd_mel_log_compress_f32(const float* mel, long long ld, float* out, int B
                                float clip, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
+ * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are
+ * t2amd_gemm_f32 calls (precision 0 exact f32 or 1 split-bf16):
+ *   frames[r][L] = rec[r][2Fp] . IB[L][2Fp]^T     IB = windowed pinv(scale * fourier_basis), columns interleaved
+ *   spec[r][2F]  = padded-as-[R][L] (lda = hop) . FB[2F][L]^T      FB rows interleaved (re, im)
+ * Complex rows are interleaved: [2f] real, [2f+1] imaginary; columns 2F .. 2Fp of rec are zero.
+ * Packed frame space: utterance b (n_b frames) owns rows [row0_b, row0_b + n_b + ceil(L/hop) - 1) and its
+ * reflect-padded signal starts at sample row0_b * hop of one packed buffer.  `plan` (int32, device) is
+ *   [row0_0 .. row0_{B-1}, R | n_0 .. n_{B-1} | utterance of row 0 .. R-1]   (2B + 1 + R entries);
+ * `n_host` is the same n_b on the host, checked by every entry point: (n_b - 1) * hop > L / 2 (reflect padding)
+ * and sum(n_b + ceil(L/hop) - 1) == R.  All launches are 1-D grid-stride: no 65,535-row limit.
+ * ------------------------------------------------------------------------------------ */
+/* sum(n_b + ceil(L/hop) - 1), or -1 for bad arguments (host only) */
+long long t2amd_gl_packed_rows(const int* n_host, int B, int L, int hop);
+/* Overlap-add of the inverse transform: every output sample sums the frames that cover it in ascending frame order, is
+ * divided by the float32 window sum-square (rebuilt from the float64 squared-window table wsq[L]) where that is
+ * > tiny(float32), and is multiplied by `scale` (= L / hop).  mode 0: out = the reflect-padded packed signal of the next
+ * forward transform (out_len >= (R - 1) * hop + L samples; gaps and tail zero).  mode 1: out[b][s] (row stride ldo,
+ * s < out_len) = the trimmed signal of utterance b for s < (n_b - 1) * hop, 0 beyond. */
+int t2amd_gl_overlap_add_f32(const float* frames, long long ldf, const double* wsq, const int* plan, const int* n_host,
+                             int B, long long R, int L, int hop, float scale, float* out, long long ldo, long long out_len,
+                             int mode, void* stream);
+/* rec[r][2f, 2f+1] = S[r][f] * (re, im) / |re + i im| for valid rows and f < F ((S, 0) when |z| = 0); zeros in gap rows
+ * and pad columns.  spec, rec: 8-byte aligned, even row strides. */
+int t2amd_gl_project_f32(const float* spec, long long lds, const float* S, long long ldS, const int* plan,
+                         const int* n_host, int B, long long R, int L, int hop, int F, int Fp, float* rec, long long ldr,
+                         void* stream);
+/* rec[r][2f, 2f+1] = m (cos p, sin p) with m = mag[b][f][j], p = phase[b][f][j] ((B, F, ldn) contiguous; phase NULL: 0)
+ * for row r = row0_b + j; S[r][f] = m.  mag NULL: m is read from S instead (S is not written). */
+int t2amd_gl_rect_f32(const float* mag, const float* phase, long long ldn, const int* plan, const int* n_host, int B,
+                      long long R, int L, int hop, int F, int Fp, float* S, long long ldS, float* rec, long long ldr,
+                      void* stream);
+/* spec rows (B*n, interleaved) -> mag[b][f][j] = sqrt(re^2 + im^2), phase[b][f][j] = atan2(im, re), (B, F, n) contiguous;
+ * either output may be NULL. */
+int t2amd_stft_polar_f32(const float* spec, long long lds, int B, int n, int F, float* mag, float* phase, void* stream);
+/* out[(b*n + j)*ld + m] = exp(mel[b][m][j]) for m < n_mel and j < lengths[b] (device; NULL: every j), 0 otherwise:
+ * the inverse of t2amd_mel_log_compress_f32.  n_host: the lengths on the host (for the checks) when lengths is set. */
+int t2amd_mel_decompress_f32(const float* mel, int B, int n_mel, int n, const int* lengths, const int* n_host, float* out,
+                             long long ld, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Optimiser step: global-norm clipping + Adam over all parameter
  * tensors in two launches.  Replaces reference train.py:233-236
  *   grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), grad_clip_thresh)

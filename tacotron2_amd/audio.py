@@ -20,8 +20,21 @@ norm=1: Slaney's Auditory-Toolbox scale, area-normalised triangles), which the r
 layers.py:50-51; librosa is not vendored in the reference and not installed here, so the published
 algorithm is restated in ``mel_filterbank`` (parity for this table is unpinned by any reference
 artefact; the STFT/magnitude/log part is pinned against the reference's own stft.py run on CPU,
-tests/golden/make_golden_audio.py).  The inverse STFT / Griffin-Lim (stft.py:107-141) is only
-used by the notebook's vocoder hand-off and is out of scope.
+tests/golden/make_golden_audio.py).
+
+mel -> wav (Griffin-Lim, reference audio_processing.py:59-76 and stft.py:77-141), also on the GPU:
+``STFT.transform`` returns (magnitude, phase), ``STFT.inverse`` / ``STFT.forward`` invert it, ``griffin_lim``
+iterates the two over a ragged batch, ``TacotronSTFT.mel_to_magnitude`` / ``TacotronSTFT.vocode`` start from
+log-mels.  One iteration on the whole batch is four launches on one stream (csrc/vocoder.hip, gemm.hip):
+  1. frames = rec . IB^T on the GEMM (IB = the reference's windowed pinv(scale * fourier_basis), built lazily in
+     float64 and cached per geometry; not a module buffer, so building a TacotronSTFT stays cheap)
+  2. overlap-add: ascending frame order, the float32 window sum-square rebuilt on the fly, / where > tiny, * L/hop,
+     written straight into the reflect-padded input of the next forward transform
+  3. spec = padded (lda = hop) . FB^T on the GEMM, exactly as the mel path
+  4. projection rec = S * z / |z| (no angle, cos or sin inside the loop)
+Ragged batches run in one packed frame space (utterance b owns n_b + ceil(L/hop) - 1 consecutive rows), so the GEMMs
+cover sum(n_b + 3) rows at L = 1024, hop = 256, not B * n_max.  The mel inversion is the clamped pseudo-inverse
+max(pinv(mel_basis) . exp(mel), 0) (the reference gives no recipe).
 """
 import os
 
@@ -88,8 +101,75 @@ def fourier_basis(filter_length, win_length, window='hann'):
     return basis
 
 
+def _pad_center(data, size):
+    lpad = (size - data.shape[-1]) // 2
+    return np.pad(data, (lpad, size - data.shape[-1] - lpad), mode='constant')
+
+
+def _squared_window(window, win_length, n_fft):
+    """float64 squared window zero-padded (centred) to n_fft: ``win_sq`` of the reference's window_sumsquare."""
+    from scipy.signal import get_window
+    return _pad_center(get_window(window, win_length, fftbins=True) ** 2, n_fft)
+
+
+def window_sumsquare(window, n_frames, hop_length=200, win_length=800, n_fft=800, dtype=np.float32, norm=None):
+    """Sum-square envelope of the window at this hop (reference audio_processing.py:7-51, librosa 0.6), on the host.
+    Only ``norm=None`` (what the reference's callers use) is supported."""
+    if norm is not None:
+        raise ValueError("window_sumsquare: only norm=None is supported")
+    if win_length is None:
+        win_length = n_fft
+    n = n_fft + hop_length * (n_frames - 1)
+    x = np.zeros(n, dtype=dtype)
+    win_sq = _squared_window(window, win_length, n_fft)
+    for i in range(n_frames):
+        sample = i * hop_length
+        x[sample:min(n, sample + n_fft)] += win_sq[:max(0, min(n_fft, n - sample))]
+    return x
+
+
+def dynamic_range_decompression(x, C=1):
+    """exp(x) / C (reference audio_processing.py:87-93)."""
+    return torch.exp(x) / C
+
+
+_INVERSE_BASES = {}
+
+
+def inverse_basis(filter_length, hop_length, win_length, window='hann'):
+    """(2F, filter_length) float32: the reference's ``inverse_basis`` (stft.py:57-70): float32(pinv(L/hop * [Re; Im]
+    fft(eye(L))[:F]).T) times the float32 window.  pinv of a 1026 x 1024 float64 matrix takes about a second on a CPU:
+    built on first use and cached per geometry (read-only array)."""
+    key = (int(filter_length), int(hop_length), int(win_length), window)
+    ib = _INVERSE_BASES.get(key)
+    if ib is None:
+        L = key[0]
+        if win_length > L:
+            raise AssertionError("filter_length must be >= win_length")
+        from scipy.signal import get_window
+        cutoff = L // 2 + 1
+        fb = np.fft.fft(np.eye(L))
+        fb = np.vstack([np.real(fb[:cutoff, :]), np.imag(fb[:cutoff, :])])
+        ib = np.linalg.pinv((L / hop_length) * fb).T.astype(np.float32)
+        if window is not None:
+            ib = ib * _pad_center(get_window(window, win_length, fftbins=True), L).astype(np.float32)[None, :]
+        ib = np.ascontiguousarray(ib, dtype=np.float32)
+        ib.setflags(write=False)
+        _INVERSE_BASES[key] = ib
+    return ib
+
+
+def packed_rows(lengths, filter_length=1024, hop_length=256):
+    """Rows of the packed frame space of a ragged batch: sum(n_b + ceil(L/hop) - 1)."""
+    c = -(-int(filter_length) // int(hop_length))
+    return int(sum(int(n) + c - 1 for n in lengths))
+
+
+_PRECISIONS = {'fp32': 0, 'bf16x3': 1}
+
+
 class STFT(torch.nn.Module):
-    """Forward transform (magnitude) of reference stft.py:42-105 on the GPU."""
+    """reference stft.py:42-141 on the GPU: forward transform (magnitude, phase), inverse, reconstruction."""
 
     def __init__(self, filter_length=800, hop_length=200, win_length=800, window='hann'):
         super().__init__()
@@ -97,6 +177,28 @@ class STFT(torch.nn.Module):
         self.cutoff = filter_length // 2 + 1
         basis = torch.from_numpy(fourier_basis(filter_length, win_length, window))
         self.register_buffer('forward_basis', basis[:, None, :].contiguous())      # (2F, 1, L) like the reference
+        self._gl_tables = {}            # per device: interleaved bases, squared window (plain attributes, not buffers)
+
+    def gl_tables(self, device):
+        """Device tables of the inverse / Griffin-Lim path, built on first use: ``fbi`` (2F, L) forward basis with re/im
+        rows interleaved, ``ibt`` (L, 2Fp) inverse basis transposed with interleaved columns (zero beyond 2F), ``wsq``
+        (L,) float64 squared window."""
+        device = torch.device(device)
+        t = self._gl_tables.get(device)
+        if t is None:
+            L, F = self.filter_length, self.cutoff
+            Fp = (F + 15) // 16 * 16
+            fb = self.forward_basis.view(2 * F, L).to(device)
+            perm = torch.stack([torch.arange(F), torch.arange(F) + F], 1).reshape(-1).to(device)
+            ib = inverse_basis(L, self.hop_length, self.win_length, self.window)
+            ibt = np.zeros((L, 2 * Fp), dtype=np.float32)
+            ibt[:, 0:2 * F:2] = ib[:F].T
+            ibt[:, 1:2 * F:2] = ib[F:].T
+            wsq = _squared_window(self.window, self.win_length, L) if self.window is not None else np.ones(L)
+            t = {"fbi": fb.index_select(0, perm).contiguous(), "ibt": torch.from_numpy(ibt).to(device),
+                 "wsq": torch.from_numpy(np.ascontiguousarray(wsq, dtype=np.float64)).to(device), "Fp": Fp}
+            self._gl_tables[device] = t
+        return t
 
     def magnitude_rows(self, y):
         """y (B, T) device f32 -> (mag (B*n, Fpad) with zero columns beyond F, n)."""
@@ -126,6 +228,136 @@ class STFT(torch.nn.Module):
         return out
 
 
+    def _spec_rows(self, y):
+        """y (B, T) device f32 -> (spec (B*n, 2Fp) interleaved re/im rows, n)."""
+        B, T = y.shape
+        L, hop, F = self.filter_length, self.hop_length, self.cutoff
+        if T <= L // 2:
+            raise ValueError("signal of %d samples is too short to reflect-pad by %d" % (T, L // 2))
+        tab = self.gl_tables(y.device)
+        Fp = tab["Fp"]
+        n = T // hop + 1
+        ldo = (T + L + 3) // 4 * 4
+        padded = torch.empty(B, ldo, dtype=torch.float32, device=y.device)
+        nv.reflect_pad(y, padded, L // 2)
+        spec = torch.empty(B * n, 2 * Fp, dtype=torch.float32, device=y.device)
+        frames0 = padded.as_strided((n, L), (hop, 1))
+        nv.gemm(spec[:n, :2 * F], frames0, tab["fbi"], batch=B, strides=(ldo, 0, n * 2 * Fp))
+        return spec, n
+
+    def transform(self, input_data):
+        """(magnitude, phase), each (B, F, n): reference stft.py:77-105 (phase = atan2(im, re))."""
+        y = _device_signal(input_data, self.forward_basis)
+        spec, n = self._spec_rows(y)
+        B, F = y.shape[0], self.cutoff
+        mag = torch.empty(B, F, n, dtype=torch.float32, device=y.device)
+        phase = torch.empty(B, F, n, dtype=torch.float32, device=y.device)
+        nv.stft_polar(spec, B, n, F, mag, phase)
+        self.num_samples = y.shape[1]
+        return mag, phase
+
+    def inverse(self, magnitude, phase):
+        """(B, 1, (n-1) hop) signal from (B, F, n) magnitude and phase: reference stft.py:107-141."""
+        out = _GriffinLim(self, magnitude, phase, None, 'fp32').run(0)
+        return out.unsqueeze(1)
+
+    def forward(self, input_data):
+        self.magnitude, self.phase = self.transform(input_data)
+        return self.inverse(self.magnitude, self.phase)
+
+
+class _GriffinLim:
+    """One Griffin-Lim call over a ragged batch in the packed frame space.  Every buffer is allocated here, once; the
+    iteration loop (run) issues four launches per iteration and no allocation, copy or synchronisation."""
+
+    def __init__(self, stft, magnitudes, angles, lengths, precision):
+        if precision not in _PRECISIONS:
+            raise ValueError("precision must be one of %s, got %r" % (sorted(_PRECISIONS), precision))
+        self.fast = _PRECISIONS[precision]
+        basis = stft.forward_basis
+        if not basis.is_cuda and not nv.validate_only():
+            raise nv.NativeError("tacotron2_amd.audio: move the module to the MI355X first (.cuda()); there is no CPU path")
+        dev = basis.device
+        L, hop, F = stft.filter_length, stft.hop_length, stft.cutoff
+        mag = magnitudes.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if mag.dim() != 3 or mag.shape[1] != F:
+            raise ValueError("expected (B, %d, n) magnitudes, got shape %s" % (F, tuple(mag.shape)))
+        B, _, n = mag.shape
+        if lengths is None:
+            lens = [n] * B
+        else:
+            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+            if len(lens) != B:
+                raise ValueError("%d lengths for a batch of %d" % (len(lens), B))
+            if min(lens) < 1 or max(lens) > n:
+                raise ValueError("lengths must lie in [1, %d], got %s" % (n, lens))
+        ph = None
+        if angles is not None:
+            ph = torch.as_tensor(angles).detach().to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(ph.shape) != tuple(mag.shape):
+                raise ValueError("angles %s do not match the magnitudes %s" % (tuple(ph.shape), tuple(mag.shape)))
+        tab = stft.gl_tables(dev)
+        Fp = tab["Fp"]
+        c = -(-L // hop)
+        rows = np.asarray(lens, dtype=np.int64) + c - 1
+        row0 = np.concatenate([[0], np.cumsum(rows)])
+        R = int(row0[-1])
+        plan = np.concatenate([row0, lens, np.repeat(np.arange(B), rows)]).astype(np.int32)
+        self.stft, self.tab, self.B, self.R, self.F, self.Fp, self.L, self.hop = stft, tab, B, R, F, Fp, L, hop
+        self.lens = nv._host_ints(lens)
+        self.T = (max(lens) - 1) * hop
+        self.plan = torch.from_numpy(plan).to(dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.S = torch.empty(R, Fp, **f32)
+        self.rec = torch.empty(R, 2 * Fp, **f32)
+        self.frames = torch.empty(R, L, **f32)
+        self.out = torch.empty(B, max(self.T, 1), **f32)
+        self.mag, self.ph = mag, ph
+        self.scale = float(L) / hop
+        self.padded = self.spec = None
+
+    def _inverse_frames(self):
+        nv.gemm(self.frames, self.rec, self.tab["ibt"], fast=self.fast)
+
+    def run(self, n_iters):
+        lens, plan, R, L, hop, F, Fp = self.lens, self.plan, self.R, self.L, self.hop, self.F, self.Fp
+        nv.gl_rect(self.mag, self.ph, plan, lens, R, L, hop, F, Fp, self.S, self.rec)
+        if n_iters > 0:
+            P = (R * hop + L + 3) // 4 * 4
+            self.padded = torch.empty(P, dtype=torch.float32, device=self.frames.device)
+            self.spec = torch.empty(R, 2 * Fp, dtype=torch.float32, device=self.frames.device)
+            view = self.padded.as_strided((R, L), (hop, 1))
+            spec_n = self.spec[:, :2 * F]
+            fbi, wsq = self.tab["fbi"], self.tab["wsq"]
+            for _ in range(n_iters):
+                self._inverse_frames()
+                nv.gl_overlap_add(self.frames, wsq, plan, lens, R, L, hop, self.scale, self.padded, 0)
+                nv.gemm(spec_n, view, fbi, fast=self.fast)
+                nv.gl_project(self.spec, self.S, plan, lens, R, L, hop, F, Fp, self.rec)
+        self._inverse_frames()
+        if self.T == 0:
+            return self.out[:, :0]
+        nv.gl_overlap_add(self.frames, self.tab["wsq"], plan, lens, R, L, hop, self.scale, self.out, 1)
+        return self.out
+
+
+def griffin_lim(magnitudes, stft_fn, n_iters=30, angles=None, lengths=None, precision='fp32'):
+    """Reference audio_processing.py:59-76 on the GPU, over a ragged batch.
+
+    magnitudes (B, F, n); stft_fn: this module's ``STFT`` (e.g. ``TacotronSTFT.stft_fn``).  ``angles`` (B, F, n) are the
+    initial phases; when None they are drawn exactly as the reference draws them,
+    ``np.angle(np.exp(2j pi np.random.rand(B, F, n))).astype(float32)``, so ``np.random.seed(s)`` gives the reference's
+    start.  ``lengths`` (B ints): utterance b uses its first n_b frames only, and its output is the signal of those
+    alone.  Returns (B, (max n_b - 1) hop) on the GPU, zero beyond each (n_b - 1) hop.  ``precision``: 'fp32' (exact f32
+    GEMMs) or 'bf16x3' (split-bf16 GEMMs)."""
+    if not isinstance(stft_fn, STFT):
+        raise TypeError("griffin_lim needs a tacotron2_amd.audio.STFT (e.g. TacotronSTFT.stft_fn)")
+    if angles is None:
+        angles = np.angle(np.exp(2j * np.pi * np.random.rand(*magnitudes.size())))
+        angles = torch.from_numpy(angles.astype(np.float32))
+    return _GriffinLim(stft_fn, magnitudes, angles, lengths, precision).run(int(n_iters))
+
+
 def _device_signal(y, like):
     if y.dim() != 2:
         raise ValueError("expected (B, T) samples, got shape %s" % (tuple(y.shape),))
@@ -148,6 +380,7 @@ class TacotronSTFT(torch.nn.Module):
         padded = torch.zeros(n_mel_channels, Fpad, dtype=torch.float32)
         padded[:, :F] = self.mel_basis
         self.register_buffer('_mel_basis_padded', padded, persistent=False)
+        self._mel_pinv = {}             # per device, built on first use by mel_to_magnitude (not a buffer)
         self.clip_val = 1e-5
         if torch.cuda.is_available():
             self.cuda()
@@ -159,6 +392,50 @@ class TacotronSTFT(torch.nn.Module):
 
     def spectral_de_normalize(self, magnitudes):
         return torch.exp(magnitudes)
+
+    def mel_pinv(self, device):
+        """(F, n_mel) float32 pseudo-inverse of the mel filterbank (float64 pinv of the float32 ``mel_basis``), built on
+        first use (not a buffer)."""
+        device = torch.device(device)
+        p = self._mel_pinv.get(device)
+        if p is None:
+            p = torch.from_numpy(np.linalg.pinv(self.mel_basis.cpu().double().numpy()).astype(np.float32)).to(device)
+            self._mel_pinv[device] = p
+        return p
+
+    def mel_to_magnitude(self, mel, lengths=None):
+        """Log-mel (B, n_mel, n) -> linear magnitudes (B, F, n) = max(pinv(mel_basis) . exp(mel), 0), zero beyond
+        ``lengths``.  The reference has no recipe for this step; the clamped pseudo-inverse is the least-squares
+        inverse of the filterbank.  fp16 / bf16 mels are cast to float32."""
+        if mel.dim() != 3 or mel.shape[1] != self.n_mel_channels:
+            raise ValueError("expected (B, %d, n) log-mels, got shape %s" % (self.n_mel_channels, tuple(mel.shape)))
+        if not self.mel_basis.is_cuda:
+            raise nv.NativeError("tacotron2_amd.audio: move the module to the MI355X first (.cuda()); there is no CPU path")
+        dev = self.mel_basis.device
+        mel = mel.detach().to(device=dev, dtype=torch.float32).contiguous()
+        B, n_mel, n = mel.shape
+        F = self.stft_fn.cutoff
+        Fp = (F + 15) // 16 * 16
+        lens_dev = lens = None
+        if lengths is not None:
+            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+            if len(lens) != B:
+                raise ValueError("%d lengths for a batch of %d" % (len(lens), B))
+            lens_dev = torch.tensor(lens, dtype=torch.int32).to(dev)
+        ldk = (n_mel + 3) // 4 * 4
+        rows = torch.empty(B * n, ldk, dtype=torch.float32, device=dev)
+        nv.mel_decompress(mel, rows, lens, lens_dev)
+        lin = torch.empty(B * n, Fp, dtype=torch.float32, device=dev)
+        nv.gemm(lin[:, :F], rows[:, :n_mel], self.mel_pinv(dev), act=1)
+        out = torch.empty(B, F, n, dtype=torch.float32, device=dev)
+        nv.transpose(out.view(-1, n)[:F], lin[:n, :F], batch=B, sstride=n * Fp, dstride=F * n)
+        return out
+
+    def vocode(self, mel, lengths=None, n_iters=30, precision='fp32', angles=None):
+        """Log-mel (B, n_mel, n) -> waveform (B, (max n_b - 1) hop) in [-1, 1]-ish units on the GPU: mel_to_magnitude,
+        then ``griffin_lim`` (initial angles drawn like the reference's when ``angles`` is None)."""
+        mag = self.mel_to_magnitude(mel, lengths)
+        return griffin_lim(mag, self.stft_fn, n_iters=n_iters, angles=angles, lengths=lengths, precision=precision)
 
     def mel_spectrogram(self, y, check_range=True):
         """y (B, T) float in [-1, 1] -> (B, n_mel_channels, T // hop + 1) on the GPU."""

@@ -285,6 +285,8 @@ SYMBOLS = [
     "t2amd_lstm_seq_batch_persistent_flag_bytes", "t2amd_lstm_seq_batch_persistent_supported", "t2amd_lstm_seq_fwd2_batch_persistent_f32", "t2amd_encoder_handoff_timeouts",
     "t2amd_lstm_seq_bwd2_batch_persistent_supported", "t2amd_lstm_seq_bwd2_batch_persistent_f32",
     "t2amd_reflect_pad_f32", "t2amd_reflect_index", "t2amd_stft_magnitude_f32", "t2amd_mel_log_compress_f32",
+    "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
+    "t2amd_mel_decompress_f32",
     "t2amd_optim_chunk", "t2amd_grad_norm_f32", "t2amd_adam_step_f32",
     "t2amd_decoder_persist_mailbox_bytes", "t2amd_decoder_persist_supported", "t2amd_decoder_infer_persistent_f32",
     "t2amd_loss_workspace_doubles", "t2amd_tacotron2_loss_fwd_f32", "t2amd_tacotron2_loss_bwd_f32",
@@ -379,6 +381,11 @@ def _argtypes():
         "t2amd_reflect_pad_f32": [_P, _L, _P, _L, _I, _I, _I, _I, _P],
         "t2amd_stft_magnitude_f32": [_P, _L, _P, _L, _L, _I, _I, _P],
         "t2amd_mel_log_compress_f32": [_P, _L, _P, _I, _I, _I, _F, _P],
+        "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
+        "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
+        "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
+        "t2amd_stft_polar_f32": [_P, _L, _I, _I, _I, _P, _P, _P],
+        "t2amd_mel_decompress_f32": [_P, _I, _I, _I, _P, _P, _P, _L, _P],
         "t2amd_optim_chunk": [],
         "t2amd_grad_norm_f32": [pt(TensorList), _F, _P, _P, _P],
         "t2amd_adam_step_f32": [pt(TensorList), pt(AdamHyper), _P, _P],
@@ -419,6 +426,8 @@ def load():
     lib.t2amd_last_error.restype = C.c_char_p
     lib.t2amd_reflect_index.argtypes = [_L, _L]
     lib.t2amd_reflect_index.restype = C.c_longlong
+    lib.t2amd_gl_packed_rows.argtypes = [_P, _I, _I, _I]
+    lib.t2amd_gl_packed_rows.restype = C.c_longlong
     lib.t2amd_abi_version.restype = C.c_int
     lib.t2amd_attn_bwd_ws_floats.restype = C.c_longlong
     lib.t2amd_attn_fwd_ws_floats.restype = C.c_longlong
@@ -1583,6 +1592,82 @@ def mel_log_compress(mel, out, clip):
         raise NativeError("mel_log_compress: shape mismatch mel=%s out=%s" % (tuple(mel.shape), tuple(out.shape)))
     _check(load().t2amd_mel_log_compress_f32(pm, _i64(ld), ptr(_fullc(out)), B, n, n_mel, C.c_float(clip), _stream()),
            "t2amd_mel_log_compress_f32")
+
+
+# ----------------------------------------------------------------------------
+# Griffin-Lim vocoder (csrc/vocoder.hip)
+# ----------------------------------------------------------------------------
+def _host_ints(values):
+    """Host int32 array of the lengths (passed through when it already is one: the Griffin-Lim loop builds it once)."""
+    if isinstance(values, C.Array):
+        return values
+    vals = [int(v) for v in values]
+    if not vals:
+        raise NativeError("empty length list")
+    return (C.c_int * len(vals))(*vals)
+
+
+def gl_packed_rows(lengths, L, hop):
+    """sum(n_b + ceil(L/hop) - 1): rows of the packed frame space (-1 for bad arguments)."""
+    n = _host_ints(lengths)
+    return int(load().t2amd_gl_packed_rows(n, len(n), int(L), int(hop)))
+
+
+def gl_overlap_add(frames, wsq, plan, lengths, R, L, hop, scale, out, mode, out_len=None):
+    """mode 0: out (1-D, packed reflect-padded signal); mode 1: out (B, T) trimmed signal (zero beyond each T_b)."""
+    pf, ldf, _, _ = _mat(frames)
+    n = _host_ints(lengths)
+    if mode == 0:
+        po, ldo, olen = ptr(_fullc(out)), 0, out.numel() if out_len is None else out_len
+    else:
+        po, ldo, _, olen = _mat(out)
+    _check(load().t2amd_gl_overlap_add_f32(pf, _i64(ldf), ptr(wsq, torch.float64), ptr(plan, torch.int32), n,
+                                           len(n), _i64(R), int(L), int(hop), C.c_float(scale), po, _i64(ldo), _i64(olen),
+                                           int(mode), _stream()), "t2amd_gl_overlap_add_f32")
+
+
+def gl_project(spec, S, plan, lengths, R, L, hop, F, Fp, rec):
+    ps, lds, _, _ = _mat(spec)
+    pS, ldS, _, _ = _mat(S)
+    pr, ldr, _, _ = _mat(rec)
+    n = _host_ints(lengths)
+    _check(load().t2amd_gl_project_f32(ps, _i64(lds), pS, _i64(ldS), ptr(plan, torch.int32), n, len(n), _i64(R),
+                                       int(L), int(hop), int(F), int(Fp), pr, _i64(ldr), _stream()), "t2amd_gl_project_f32")
+
+
+def gl_rect(mag, phase, plan, lengths, R, L, hop, F, Fp, S, rec):
+    """mag/phase (B, F, n) contiguous (phase None: 0; mag None: magnitudes already in S)."""
+    src = mag if mag is not None else phase
+    ldn = src.shape[-1] if src is not None else 0
+    pS, ldS, _, _ = _mat(S)
+    pr, ldr, _, _ = _mat(rec)
+    n = _host_ints(lengths)
+    _check(load().t2amd_gl_rect_f32(ptr(_fullc(mag)) if mag is not None else None,
+                                    ptr(_fullc(phase)) if phase is not None else None, _i64(ldn), ptr(plan, torch.int32),
+                                    n, len(n), _i64(R), int(L), int(hop), int(F), int(Fp), pS, _i64(ldS), pr,
+                                    _i64(ldr), _stream()), "t2amd_gl_rect_f32")
+
+
+def stft_polar(spec, B, n, F, mag, phase):
+    """spec rows (B*n, interleaved re/im) -> mag, phase (B, F, n)."""
+    ps, lds, R, _ = _mat(spec)
+    if R != B * n:
+        raise NativeError("stft_polar: %d spectrum rows for B=%d, n=%d" % (R, B, n))
+    _check(load().t2amd_stft_polar_f32(ps, _i64(lds), int(B), int(n), int(F),
+                                       ptr(_fullc(mag)) if mag is not None else None,
+                                       ptr(_fullc(phase)) if phase is not None else None, _stream()), "t2amd_stft_polar_f32")
+
+
+def mel_decompress(mel, out, lengths=None, lengths_dev=None):
+    """out (B*n, ld) = exp(mel (B, n_mel, n)) transposed, zero beyond lengths and n_mel."""
+    B, n_mel, n = mel.shape
+    po, ld, R, _ = _mat(out)
+    if R != B * n:
+        raise NativeError("mel_decompress: shape mismatch mel=%s out=%s" % (tuple(mel.shape), tuple(out.shape)))
+    nh = _host_ints(lengths) if lengths is not None else None
+    _check(load().t2amd_mel_decompress_f32(ptr(_fullc(mel)), B, n_mel, n,
+                                           ptr(lengths_dev, torch.int32) if lengths_dev is not None else None, nh, po,
+                                           _i64(ld), _stream()), "t2amd_mel_decompress_f32")
 
 
 # ----------------------------------------------------------------------------

@@ -1,0 +1,64 @@
+"""mel -> wav with Griffin-Lim on the GPU.
+
+    python -m tacotron2_amd.vocode MEL.npy [MEL.npy ...] -o DIR [--iters N] [--precision fp32|bf16x3] [--seed S]
+
+Reads (n_mel, n) float32 log-mels (what ``precompute_mels`` writes) or (B, n_mel, n) batches (one wav per item,
+``<stem>_<b>.wav``), vocodes them as one ragged batch (``TacotronSTFT.vocode``) and writes ``DIR/<stem>.wav``:
+16-bit PCM at ``hparams.sampling_rate``, the signal clipped to [-1, 1] and scaled by ``max_wav_value``.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m tacotron2_amd.vocode", description=__doc__.split("\n\n")[0])
+    ap.add_argument("mels", nargs="+", help="(n_mel, n) or (B, n_mel, n) float32 .npy log-mel files")
+    ap.add_argument("-o", "--out-dir", required=True)
+    ap.add_argument("--iters", type=int, default=30, help="Griffin-Lim iterations (default 30)")
+    ap.add_argument("--precision", choices=("fp32", "bf16x3"), default="fp32")
+    ap.add_argument("--seed", type=int, default=None, help="np.random.seed before the initial angles are drawn")
+    ap.add_argument("--hparams", default="", help="comma-separated name=value overrides")
+    args = ap.parse_args(argv)
+    from .audio import TacotronSTFT
+    from .hparams import create_hparams
+    hp = create_hparams(args.hparams)
+    mels, names = [], []
+    for p in args.mels:
+        m = np.load(p).astype(np.float32)
+        stem = os.path.splitext(os.path.basename(p))[0]
+        if m.ndim == 3 and m.shape[1] == hp.n_mel_channels:          # a (B, n_mel, n) batch: one wav per item
+            mels += list(m)
+            names += ["%s_%d" % (stem, b) for b in range(m.shape[0])]
+        elif m.ndim == 2 and m.shape[0] == hp.n_mel_channels:
+            mels.append(m)
+            names.append(stem)
+        else:
+            raise SystemExit("%s: expected (%d, n) or (B, %d, n) log-mels, got shape %s"
+                             % (p, hp.n_mel_channels, hp.n_mel_channels, m.shape))
+    lengths = [m.shape[1] for m in mels]
+    batch = np.zeros((len(mels), hp.n_mel_channels, max(lengths)), np.float32)
+    for b, m in enumerate(mels):
+        batch[b, :, :m.shape[1]] = m
+    stft = TacotronSTFT(hp.filter_length, hp.hop_length, hp.win_length, hp.n_mel_channels, hp.sampling_rate,
+                        hp.mel_fmin, hp.mel_fmax)
+    if args.seed is not None:
+        np.random.seed(args.seed)
+    wav = stft.vocode(torch.from_numpy(batch), lengths=lengths, n_iters=args.iters, precision=args.precision).cpu().numpy()
+    from scipy.io.wavfile import write
+    os.makedirs(args.out_dir, exist_ok=True)
+    for b, name in enumerate(names):
+        T = (lengths[b] - 1) * hp.hop_length
+        # [-1, 1] * max_wav_value, kept inside int16 (1.0 * 32768 would wrap)
+        pcm = np.clip(np.clip(wav[b, :T], -1.0, 1.0) * hp.max_wav_value, -32768, 32767).astype(np.int16)
+        dst = os.path.join(args.out_dir, name + ".wav")
+        write(dst, hp.sampling_rate, pcm)
+        print(dst, T, "samples")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
