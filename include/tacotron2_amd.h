@@ -949,6 +949,37 @@ int t2amd_mel_decompress_f32(const float* mel, int B, int n_mel, int n, const in
                              long long ld, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * WaveGlow inference (csrc/waveglow.hip, csrc/waveglow_layer.hip; tacotron2_amd/waveglow.py).  NVIDIA's glow.py is not
+ * part of the reference checkout: the arithmetic these passes follow is restated in tests/waveglow_ref.py.
+ * Packed row space: utterance b's rows (n_group samples each) sit between zero halos of `halo` rows, [halo | R_0 | halo |
+ * ... | R_{B-1} | halo]; rowb[p] is the utterance of packed row p (-1 in a halo), rowr[p] its row in the utterance.
+ * ------------------------------------------------------------------------------------ */
+/* One WN layer product over M rows of the image X (row stride ldx, X at the first computed row; the image carries a zero
+ * halo of at least dil rows on both sides).  W [N][taps * Cin], K tap-major: column tap * Cin + c reads
+ * X[(m + (tap - (taps-1)/2) * dil) * ldx + c].  precision 0 exact f32, 1 split-bf16 x3, 2 bf16.
+ * mode 0 (gated, N = 2C, C a multiple of 64): W rows / bias packed so that block 64q .. 64q+31 holds tanh channels
+ *   32q .. 32q+31 and 64q+32 .. 64q+63 their sigmoid partners;  acts[m][c] = tanh(. + cnd[m][c]) * sigmoid(. + cnd[m][C+c])
+ *   with cnd in the original column order.
+ * mode 1 (residual / skip, taps 1): column n < nres: h[m][n] += . (rows with rowb[m] >= 0 only); n >= nres:
+ *   skip[m][n - nres] = . (skip_store) or += . */
+int t2amd_wg_layer_f32(const float* X, long long ldx, const float* W, const float* bias, int M, int N, int Cin, int taps,
+                       int dil, int mode, const float* cnd, long long ldcnd, float* acts, long long ldacts, float* h,
+                       long long ldh, int nres, float* skip, long long ldskip, int skip_store, const int* rowb,
+                       int precision, void* stream);
+/* Flow tail over P packed rows (rows with rowb >= 0), f32: e = end_b + end_w[n_in][C] . skip[p];
+ * x1 = (x1 - e[:n_in/2]) / exp(e[n_in/2:]) on x = audio[p][0:n_in]; y = winv[n_in][n_in] . x;
+ * a = [sigma * z[b*zb + k*zc + r] for k < n_new ; y] (z NULL: a = y; end_w NULL: a = the noise alone, the first call);
+ * out[b*ldout + n_group*r + g] = a[g] when out is set (the waveform, after flow 0), else audio[p] = a;
+ * h[p][c] = start_b[c] + start_w[c][0:n_out/2] . a when start_w is set.  C <= 512, even n_group <= 16. */
+int t2amd_wg_tail_f32(const float* skip, long long ldskip, int C, const float* end_w, const float* end_b, int n_in,
+                      const float* winv, float* audio, long long ldaudio, const float* z, long long zb, long long zc,
+                      int n_new, float sigma, const float* start_w, const float* start_b, float* h, long long ldh,
+                      float* out, long long ldout, const int* rowb, const int* rowr, long long P, int n_group,
+                      void* stream);
+/* Denoiser (reference denoiser.py): mag[b][f][t] = max(mag - bias[f] * strength, 0) in place, mag (B, F, n) contiguous. */
+int t2amd_wg_denoise_f32(float* mag, const float* bias, int B, int F, long long n, float strength, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Optimiser step: global-norm clipping + Adam over all parameter
  * tensors in two launches.  Replaces reference train.py:233-236
  *   grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), grad_clip_thresh)

@@ -1,0 +1,320 @@
+// WaveGlow WN layer products on the MFMA (see waveglow.hip for the layout and the rest of the inference path).
+//
+// One kernel body per precision, both with 128 x 128 output tiles of 4 waves (2 x 2, 64 x 64 per wave = 2 x 2 MFMA tiles
+// of 32 x 32), A = the channel-last row image, B = weights [N][K] (K contiguous).  K is tap-major: column tap * Cin + c of
+// row m reads X[(m + (tap - (taps - 1) / 2) * dil) * ldx + c].  The caller points X at the first computed row of an image
+// whose zero halo is at least dil rows deep on both sides, so no tap needs a bounds test and none crosses an utterance.
+//
+// mode 0 (gated in-layer product, N = 2C, K = 3C): the weight rows are packed so that column block 64 q + 0..31 holds the
+// tanh channels 32 q .. 32 q + 31 and block 64 q + 32..63 their sigmoid partners.  A wave owns the 64 columns of one q,
+// and the 32x32 MFMA puts the column on the lane (col = lane & 31), so both partners of a channel sit in the same lane:
+//   acts[m][c] = tanh(acc_t + bias_t + cnd[m][c]) * sigmoid(acc_s + bias_s + cnd[m][C + c])
+// The 2C-wide pre-activation never leaves registers.
+// mode 1 (residual / skip product, K = C): column n < nres is added into h (rows whose rowb >= 0 only, so halo rows stay
+// zero); column n >= nres goes to skip[m][n - nres] (stored when skip_store, else added).
+//
+// Precision 0 is the exact-f32 MFMA (v_mfma_f32_32x32x2_f32), 1 split-bf16 x 3 and 2 plain bf16 on
+// v_mfma_f32_32x32x16_bf16, with the operand splitting of gemm.hip's bf16 kernels.
+#include "common.h"
+
+struct WgLayerParams {
+    const float* X;
+    long long ldx;
+    const float* W;
+    const float* bias;
+    int M, N, K, Cin, taps, dil, mode;
+    const float* cnd;
+    long long ldcnd;
+    float* acts;
+    long long ldacts;
+    float* h;
+    long long ldh;
+    int nres, skip_store;
+    float* skip;
+    long long ldskip;
+    const int* rowb;
+};
+
+__device__ __forceinline__ float wg_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// Epilogue of one wave's 64 x 64 block: acc[tm][tn] is the 32 x 32 tile at rows wm*64 + tm*32, columns wn*64 + tn*32.
+__device__ __forceinline__ void wg_layer_epilogue(const WgLayerParams& p, f32x16 (&acc)[2][2], int row0, int col0, int wm,
+                                                  int wn, int lane) {
+    const int l31 = lane & 31, lhi = lane >> 5;
+    const int cbase = col0 + wn * 64;
+    if (p.mode == 0) {
+        if (cbase >= p.N) return;
+        const int C = p.N >> 1;
+        const int c = (cbase >> 1) + l31;
+        const float bt = p.bias[cbase + l31], bs = p.bias[cbase + 32 + l31];
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int gm = row0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                if (gm < p.M) {
+                    const float* cr = p.cnd + (long long)gm * p.ldcnd;
+                    const float t = acc[tm][0][r] + bt + cr[c];
+                    const float s = acc[tm][1][r] + bs + cr[C + c];
+                    p.acts[(long long)gm * p.ldacts + c] = tanhf(t) * wg_sigmoid(s);
+                }
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) {
+        const int gn = cbase + tn * 32 + l31;
+        if (gn >= p.N) continue;
+        const float b = p.bias[gn];
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int gm = row0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                if (gm < p.M) {
+                    const float v = acc[tm][tn][r] + b;
+                    if (gn < p.nres) {
+                        if (p.rowb[gm] >= 0) {
+                            float* hp = p.h + (long long)gm * p.ldh + gn;
+                            *hp = *hp + v;
+                        }
+                    } else {
+                        float* sp = p.skip + (long long)gm * p.ldskip + (gn - p.nres);
+                        *sp = p.skip_store ? v : *sp + v;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ---- exact f32: 128 x 128 x 16 tiles, both operands transposed into k-major LDS (row stride 132) ----------------------
+#define WBK 16
+#define WLD 132
+
+__global__ __launch_bounds__(256) void wg_layer_f32_kernel(WgLayerParams p) {
+    __shared__ __attribute__((aligned(16))) float As[2][WBK][WLD];
+    __shared__ __attribute__((aligned(16))) float Bs[2][WBK][WLD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int row0 = blockIdx.y * 128, col0 = blockIdx.x * 128;
+    const int nk = p.K / WBK;
+    const int half = (p.taps - 1) / 2;
+    float4 ra[2], rb[2];
+
+    auto load = [&](int k0) {
+        const int tap = k0 / p.Cin;
+        const int off = (tap - half) * p.dil;
+        const int col = k0 - tap * p.Cin;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int f = tid + 256 * i;
+            const int r = f >> 2, kq = f & 3;
+            const int gm = row0 + r, gn = col0 + r;
+            ra[i] = gm < p.M ? *reinterpret_cast<const float4*>(p.X + (long long)(gm + off) * p.ldx + col + kq * 4)
+                             : make_float4(0.f, 0.f, 0.f, 0.f);
+            rb[i] = gn < p.N ? *reinterpret_cast<const float4*>(p.W + (long long)gn * p.K + k0 + kq * 4)
+                             : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    auto store = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int f = tid + 256 * i;
+            const int r = f >> 2, kq = f & 3;
+            As[buf][kq * 4 + 0][r] = ra[i].x;
+            As[buf][kq * 4 + 1][r] = ra[i].y;
+            As[buf][kq * 4 + 2][r] = ra[i].z;
+            As[buf][kq * 4 + 3][r] = ra[i].w;
+            Bs[buf][kq * 4 + 0][r] = rb[i].x;
+            Bs[buf][kq * 4 + 1][r] = rb[i].y;
+            Bs[buf][kq * 4 + 2][r] = rb[i].z;
+            Bs[buf][kq * 4 + 3][r] = rb[i].w;
+        }
+    };
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    load(0);
+    store(0);
+    __syncthreads();
+    const int l31 = lane & 31, lhi = lane >> 5;
+    int cur = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+        const bool more = kt + 1 < nk;
+        if (more) load((kt + 1) * WBK);
+#pragma unroll
+        for (int kk = 0; kk < WBK / 2; ++kk) {
+            const int krow = kk * 2 + lhi;
+            const float a0 = As[cur][krow][wm * 64 + l31];
+            const float a1 = As[cur][krow][wm * 64 + 32 + l31];
+            const float b0 = Bs[cur][krow][wn * 64 + l31];
+            const float b1 = Bs[cur][krow][wn * 64 + 32 + l31];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+        if (more) store(cur ^ 1);
+        __syncthreads();
+        cur ^= 1;
+    }
+    wg_layer_epilogue(p, acc, row0, col0, wm, wn, lane);
+}
+
+// ---- split-bf16 x 3 (X3) / plain bf16: 128 x 128 x 32 tiles, K-contiguous bf16 LDS rows (stride 40) ------------------
+typedef short wg_bf16x8 __attribute__((ext_vector_type(8)));
+#define WHK 32
+#define WHLD 40
+
+__device__ __forceinline__ unsigned wg_cvt_pk_bf16(float a, float b) {
+    unsigned r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+template <bool X3>
+__global__ __launch_bounds__(256) void wg_layer_bf16_kernel(WgLayerParams p) {
+    constexpr int NH = X3 ? 2 : 1;
+    constexpr int IMG = 128 * WHLD;
+    __shared__ __attribute__((aligned(16))) unsigned short As[2][NH * IMG];
+    __shared__ __attribute__((aligned(16))) unsigned short Bs[2][NH * IMG];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int row0 = blockIdx.y * 128, col0 = blockIdx.x * 128;
+    const int nk = p.K / WHK;
+    const int half = (p.taps - 1) / 2;
+    float4 ra[4], rb[4];
+
+    auto load = [&](int k0) {
+        const int tap = k0 / p.Cin;
+        const int off = (tap - half) * p.dil;
+        const int col = k0 - tap * p.Cin;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int f = tid + 256 * i;
+            const int r = f >> 3, kq = f & 7;
+            const int gm = row0 + r, gn = col0 + r;
+            ra[i] = gm < p.M ? *reinterpret_cast<const float4*>(p.X + (long long)(gm + off) * p.ldx + col + kq * 4)
+                             : make_float4(0.f, 0.f, 0.f, 0.f);
+            rb[i] = gn < p.N ? *reinterpret_cast<const float4*>(p.W + (long long)gn * p.K + k0 + kq * 4)
+                             : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    auto store_one = [&](unsigned short* S, const float4 (&v)[4]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int f = tid + 256 * i;
+            const int r = f >> 3, kq = f & 7;
+            uint2 hi;
+            hi.x = wg_cvt_pk_bf16(v[i].x, v[i].y);
+            hi.y = wg_cvt_pk_bf16(v[i].z, v[i].w);
+            *reinterpret_cast<uint2*>(&S[r * WHLD + kq * 4]) = hi;
+            if (X3) {
+                uint2 lo;
+                lo.x = wg_cvt_pk_bf16(v[i].x - __uint_as_float(hi.x << 16), v[i].y - __uint_as_float(hi.x & 0xffff0000u));
+                lo.y = wg_cvt_pk_bf16(v[i].z - __uint_as_float(hi.y << 16), v[i].w - __uint_as_float(hi.y & 0xffff0000u));
+                *reinterpret_cast<uint2*>(&S[IMG + r * WHLD + kq * 4]) = lo;
+            }
+        }
+    };
+    auto frag = [&](const unsigned short* S, int row, int ks, int lhi_) -> wg_bf16x8 {
+        return *reinterpret_cast<const wg_bf16x8*>(&S[row * WHLD + ks * 16 + lhi_ * 8]);
+    };
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    load(0);
+    store_one(As[0], ra);
+    store_one(Bs[0], rb);
+    __syncthreads();
+    const int l31 = lane & 31, lhi = lane >> 5;
+    int cur = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+        const bool more = kt + 1 < nk;
+        if (more) load((kt + 1) * WHK);
+#pragma unroll
+        for (int ks = 0; ks < WHK / 16; ++ks) {
+            wg_bf16x8 ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                ah[t] = frag(As[cur], wm * 64 + t * 32 + l31, ks, lhi);
+                bh[t] = frag(Bs[cur], wn * 64 + t * 32 + l31, ks, lhi);
+                if (X3) {
+                    al[t] = frag(As[cur] + IMG, wm * 64 + t * 32 + l31, ks, lhi);
+                    bl[t] = frag(Bs[cur] + IMG, wn * 64 + t * 32 + l31, ks, lhi);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    if (X3) {
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                    }
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+                }
+        }
+        if (more) {
+            store_one(As[cur ^ 1], ra);
+            store_one(Bs[cur ^ 1], rb);
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    wg_layer_epilogue(p, acc, row0, col0, wm, wn, lane);
+}
+
+extern "C" int t2amd_wg_layer_f32(const float* X, long long ldx, const float* W, const float* bias, int M, int N, int Cin,
+                                  int taps, int dil, int mode, const float* cnd, long long ldcnd, float* acts,
+                                  long long ldacts, float* h, long long ldh, int nres, float* skip, long long ldskip,
+                                  int skip_store, const int* rowb, int precision, void* stream) {
+    T2_REQUIRE(X && W && bias, "wg_layer: null operand");
+    T2_REQUIRE(M > 0 && N > 0 && Cin > 0 && taps >= 1 && taps % 2 == 1 && dil >= 1, "wg_layer: bad dims");
+    T2_REQUIRE(Cin % 32 == 0, "wg_layer: input channels must be a multiple of 32");
+    T2_REQUIRE(ldx >= Cin && ldx % 4 == 0 && t2_aligned16(X) && t2_aligned16(W), "wg_layer: X / W must be 16-byte aligned rows");
+    T2_REQUIRE(precision >= 0 && precision <= 2, "wg_layer: precision must be 0 (exact f32), 1 (split-bf16 x3) or 2 (bf16)");
+    WgLayerParams p;
+    p.X = X; p.ldx = ldx; p.W = W; p.bias = bias;
+    p.M = M; p.N = N; p.K = taps * Cin; p.Cin = Cin; p.taps = taps; p.dil = dil; p.mode = mode;
+    p.cnd = cnd; p.ldcnd = ldcnd; p.acts = acts; p.ldacts = ldacts;
+    p.h = h; p.ldh = ldh; p.nres = nres; p.skip_store = skip_store; p.skip = skip; p.ldskip = ldskip; p.rowb = rowb;
+    if (mode == 0) {
+        T2_REQUIRE(cnd && acts, "wg_layer: gated product needs cnd and acts");
+        T2_REQUIRE(N % 128 == 0, "wg_layer: gated product needs N = 2C with C a multiple of 64");
+        T2_REQUIRE(ldcnd >= N && ldacts >= N / 2, "wg_layer: cnd / acts rows too short");
+    } else if (mode == 1) {
+        T2_REQUIRE(taps == 1, "wg_layer: residual / skip product is 1x1");
+        T2_REQUIRE(skip && rowb, "wg_layer: residual / skip product needs skip and rowb");
+        T2_REQUIRE(nres >= 0 && nres < N, "wg_layer: nres out of range");
+        T2_REQUIRE(nres == 0 || (h && ldh >= nres), "wg_layer: residual columns need h");
+        T2_REQUIRE(ldskip >= N - nres, "wg_layer: skip rows too short");
+    } else {
+        T2_FAIL("wg_layer: mode must be 0 (gated) or 1 (residual / skip)");
+    }
+    dim3 grid(t2_cdiv(N, 128), t2_cdiv(M, 128));
+    T2_REQUIRE(grid.y <= 65535, "wg_layer: too many rows");
+    hipStream_t s = (hipStream_t)stream;
+    if (precision == 0)
+        T2_LAUNCH(wg_layer_f32_kernel, grid, dim3(256), 0, s, p);
+    else if (precision == 1)
+        T2_LAUNCH(wg_layer_bf16_kernel<true>, grid, dim3(256), 0, s, p);
+    else
+        T2_LAUNCH(wg_layer_bf16_kernel<false>, grid, dim3(256), 0, s, p);
+    T2_LAUNCH_CHECK();
+    return T2AMD_OK;
+}

@@ -287,6 +287,7 @@ SYMBOLS = [
     "t2amd_reflect_pad_f32", "t2amd_reflect_index", "t2amd_stft_magnitude_f32", "t2amd_mel_log_compress_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
+    "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32",
     "t2amd_optim_chunk", "t2amd_grad_norm_f32", "t2amd_adam_step_f32",
     "t2amd_decoder_persist_mailbox_bytes", "t2amd_decoder_persist_supported", "t2amd_decoder_infer_persistent_f32",
     "t2amd_loss_workspace_doubles", "t2amd_tacotron2_loss_fwd_f32", "t2amd_tacotron2_loss_bwd_f32",
@@ -386,6 +387,10 @@ def _argtypes():
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
         "t2amd_stft_polar_f32": [_P, _L, _I, _I, _I, _P, _P, _P],
         "t2amd_mel_decompress_f32": [_P, _I, _I, _I, _P, _P, _P, _L, _P],
+        "t2amd_wg_layer_f32": [_P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _I, _P, _L, _I, _P, _I, _P],
+        "t2amd_wg_tail_f32": [_P, _L, _I, _P, _P, _I, _P, _P, _L, _P, _L, _L, _I, _F, _P, _P, _P, _L, _P, _L, _P, _P, _L,
+                              _I, _P],
+        "t2amd_wg_denoise_f32": [_P, _P, _I, _I, _L, _F, _P],
         "t2amd_optim_chunk": [],
         "t2amd_grad_norm_f32": [pt(TensorList), _F, _P, _P, _P],
         "t2amd_adam_step_f32": [pt(TensorList), pt(AdamHyper), _P, _P],
@@ -1668,6 +1673,88 @@ def mel_decompress(mel, out, lengths=None, lengths_dev=None):
     _check(load().t2amd_mel_decompress_f32(ptr(_fullc(mel)), B, n_mel, n,
                                            ptr(lengths_dev, torch.int32) if lengths_dev is not None else None, nh, po,
                                            _i64(ld), _stream()), "t2amd_mel_decompress_f32")
+
+
+# ----------------------------------------------------------------------------
+# WaveGlow (csrc/waveglow.hip, csrc/waveglow_layer.hip)
+# ----------------------------------------------------------------------------
+def _opt(t, dtype=torch.float32):
+    return ptr(_fullc(t), dtype) if t is not None else None
+
+
+def wg_gated(X, W, bias, dil, cnd, acts, precision):
+    """acts[m][0:C] = tanh * sigmoid of the dilated kernel-3 product of the halo image X (a view whose rows continue
+    for at least `dil` rows on both sides) with the gate-packed weights W [2C][3C] (+ bias, + cnd[m][0:2C])."""
+    px, ldx, M, Cin = _mat(X)
+    pw, _, N, K = _mat(W)
+    pc, ldc, Mc, Nc = _mat(cnd)
+    pa, lda, Ma, Ca = _mat(acts)
+    if K != 3 * Cin or Mc != M or Ma != M or Nc != N or 2 * Ca != N or bias.numel() != N:
+        raise NativeError("wg_gated: shape mismatch X=%s W=%s cnd=%s acts=%s" % (tuple(X.shape), tuple(W.shape),
+                                                                                tuple(cnd.shape), tuple(acts.shape)))
+    _check(load().t2amd_wg_layer_f32(px, _i64(ldx), pw, ptr(_fullc(bias)), M, N, Cin, 3, int(dil), 0, pc, _i64(ldc), pa,
+                                     _i64(lda), None, 0, 0, None, 0, 0, None, int(precision), _stream()),
+           "t2amd_wg_layer_f32")
+
+
+def wg_res_skip(acts, W, bias, h, skip, skip_store, rowb, precision):
+    """h[m] += (acts . W^T + bias)[0:C] on rows with rowb >= 0 (h None: the last layer, no residual half);
+    skip[m] (+)= the remaining columns."""
+    px, ldx, M, Cin = _mat(acts)
+    pw, _, N, K = _mat(W)
+    ps, lds, Ms, Cs = _mat(skip)
+    nres = 0
+    ph, ldh = None, 0
+    if h is not None:
+        ph, ldh, Mh, nres = _mat(h)
+        if Mh != M:
+            raise NativeError("wg_res_skip: h rows")
+    if K != Cin or Ms != M or N - nres != Cs or bias.numel() != N or rowb.numel() < M:
+        raise NativeError("wg_res_skip: shape mismatch acts=%s W=%s skip=%s" % (tuple(acts.shape), tuple(W.shape),
+                                                                               tuple(skip.shape)))
+    _check(load().t2amd_wg_layer_f32(px, _i64(ldx), pw, ptr(_fullc(bias)), M, N, Cin, 1, 1, 1, None, 0, None, 0, ph,
+                                     _i64(ldh), nres, ps, _i64(lds), 1 if skip_store else 0, ptr(rowb, torch.int32),
+                                     int(precision), _stream()), "t2amd_wg_layer_f32")
+
+
+def wg_tail(rowb, rowr, audio, n_group, skip=None, end_w=None, end_b=None, winv=None, z=None, sigma=0.0,
+            start_w=None, start_b=None, h=None, out=None):
+    """The flow tail over every packed row (see the header).  z: the (B, n_new, R) noise tensor (contiguous);
+    start_w (C, n_half') and end_w (n_in, C) contiguous; out (B, >= n_group R) waveform rows."""
+    P = rowb.numel()
+    pa, lda, Pa, _ = _mat(audio)
+    if Pa != P or rowr.numel() != P:
+        raise NativeError("wg_tail: %d audio rows / %d rowr for %d packed rows" % (Pa, rowr.numel(), P))
+    n_in, nc = (end_w.shape[0], end_w.shape[1]) if end_w is not None else (0, 0)
+    ps, lds = None, 0
+    if skip is not None:
+        ps, lds, _, cs = _mat(skip)
+        nc = nc or cs
+    if start_w is not None:
+        nc = nc or start_w.shape[0]
+    ph, ldh = None, 0
+    if h is not None:
+        ph, ldh, _, _ = _mat(h)
+    zp, zb, zc, n_new = None, 0, 0, 0
+    if z is not None:
+        _fullc(z)
+        zp, zb, zc, n_new = ptr(z), z.stride(0), z.stride(1), z.shape[1]
+    po, ldo = None, 0
+    if out is not None:
+        po, ldo, _, _ = _mat(out)
+    _check(load().t2amd_wg_tail_f32(ps, _i64(lds), int(nc), _opt(end_w), _opt(end_b), int(n_in), _opt(winv), pa, _i64(lda),
+                                    zp, _i64(zb), _i64(zc), int(n_new), _F(sigma),
+                                    _opt(start_w), _opt(start_b), ph, _i64(ldh), po, _i64(ldo), ptr(rowb, torch.int32),
+                                    ptr(rowr, torch.int32), _i64(P), int(n_group), _stream()), "t2amd_wg_tail_f32")
+
+
+def wg_denoise(mag, bias, strength):
+    """mag (B, F, n) = max(mag - bias (F,) * strength, 0), in place."""
+    B, F, n = mag.shape
+    if bias.numel() != F:
+        raise NativeError("wg_denoise: bias has %d entries for %d bins" % (bias.numel(), F))
+    _check(load().t2amd_wg_denoise_f32(ptr(_fullc(mag)), ptr(_fullc(bias)), B, F, _i64(n), _F(strength), _stream()),
+           "t2amd_wg_denoise_f32")
 
 
 # ----------------------------------------------------------------------------

@@ -1,10 +1,13 @@
-"""mel -> wav with Griffin-Lim on the GPU.
+"""mel -> wav with Griffin-Lim or WaveGlow on the GPU.
 
     python -m tacotron2_amd.vocode MEL.npy [MEL.npy ...] -o DIR [--iters N] [--precision fp32|bf16x3] [--seed S]
+    python -m tacotron2_amd.vocode MEL.npy [...] -o DIR --waveglow CKPT [--sigma 0.666] [--denoise STRENGTH]
+                                   [--precision fp32|bf16x3|bf16] [--seed S]
 
 Reads (n_mel, n) float32 log-mels (what ``precompute_mels`` writes) or (B, n_mel, n) batches (one wav per item,
-``<stem>_<b>.wav``), vocodes them as one ragged batch (``TacotronSTFT.vocode``) and writes ``DIR/<stem>.wav``:
-16-bit PCM at ``hparams.sampling_rate``, the signal clipped to [-1, 1] and scaled by ``max_wav_value``.
+``<stem>_<b>.wav``), vocodes them as one ragged batch (``TacotronSTFT.vocode``, or ``WaveGlow.infer`` and optionally
+``Denoiser`` with ``--waveglow``: 256 samples per mel frame) and writes ``DIR/<stem>.wav``: 16-bit PCM at
+``hparams.sampling_rate``, the signal clipped to [-1, 1] and scaled by ``max_wav_value``.
 """
 import argparse
 import os
@@ -19,8 +22,14 @@ def main(argv=None):
     ap.add_argument("mels", nargs="+", help="(n_mel, n) or (B, n_mel, n) float32 .npy log-mel files")
     ap.add_argument("-o", "--out-dir", required=True)
     ap.add_argument("--iters", type=int, default=30, help="Griffin-Lim iterations (default 30)")
-    ap.add_argument("--precision", choices=("fp32", "bf16x3"), default="fp32")
-    ap.add_argument("--seed", type=int, default=None, help="np.random.seed before the initial angles are drawn")
+    ap.add_argument("--precision", choices=("fp32", "bf16x3", "bf16"), default="fp32",
+                    help="bf16 applies to WaveGlow only")
+    ap.add_argument("--seed", type=int, default=None,
+                    help="np.random.seed before the initial angles are drawn (torch.manual_seed with --waveglow)")
+    ap.add_argument("--waveglow", default=None, metavar="CKPT", help="vocode with this WaveGlow checkpoint")
+    ap.add_argument("--sigma", type=float, default=0.666, help="WaveGlow noise scale (default 0.666)")
+    ap.add_argument("--denoise", type=float, default=0.0, metavar="STRENGTH",
+                    help="WaveGlow Denoiser strength (default 0 = off)")
     ap.add_argument("--hparams", default="", help="comma-separated name=value overrides")
     args = ap.parse_args(argv)
     from .audio import TacotronSTFT
@@ -43,15 +52,28 @@ def main(argv=None):
     batch = np.zeros((len(mels), hp.n_mel_channels, max(lengths)), np.float32)
     for b, m in enumerate(mels):
         batch[b, :, :m.shape[1]] = m
-    stft = TacotronSTFT(hp.filter_length, hp.hop_length, hp.win_length, hp.n_mel_channels, hp.sampling_rate,
-                        hp.mel_fmin, hp.mel_fmax)
-    if args.seed is not None:
-        np.random.seed(args.seed)
-    wav = stft.vocode(torch.from_numpy(batch), lengths=lengths, n_iters=args.iters, precision=args.precision).cpu().numpy()
+    if args.waveglow:
+        from .waveglow import Denoiser, load_waveglow
+        wg = load_waveglow(args.waveglow).cuda().eval()
+        wg.precision = args.precision
+        if args.seed is not None:
+            torch.manual_seed(args.seed)
+        audio = wg.infer(torch.from_numpy(batch).cuda(), sigma=args.sigma, lengths=lengths)
+        if args.denoise > 0:
+            audio = Denoiser(wg)(audio, strength=args.denoise)[:, 0]
+        wav = audio.float().cpu().numpy()
+        n_samples = [256 * n for n in lengths]
+    else:
+        stft = TacotronSTFT(hp.filter_length, hp.hop_length, hp.win_length, hp.n_mel_channels, hp.sampling_rate,
+                            hp.mel_fmin, hp.mel_fmax)
+        if args.seed is not None:
+            np.random.seed(args.seed)
+        wav = stft.vocode(torch.from_numpy(batch), lengths=lengths, n_iters=args.iters, precision=args.precision).cpu().numpy()
+        n_samples = [(n - 1) * hp.hop_length for n in lengths]
     from scipy.io.wavfile import write
     os.makedirs(args.out_dir, exist_ok=True)
     for b, name in enumerate(names):
-        T = (lengths[b] - 1) * hp.hop_length
+        T = n_samples[b]
         # [-1, 1] * max_wav_value, kept inside int16 (1.0 * 32768 would wrap)
         pcm = np.clip(np.clip(wav[b, :T], -1.0, 1.0) * hp.max_wav_value, -32768, 32767).astype(np.int16)
         dst = os.path.join(args.out_dir, name + ".wav")

@@ -1,0 +1,391 @@
+"""WaveGlow inference on the MI355X: NVIDIA's vocoder (glow.py, the reference notebook's ``waveglow.infer`` and
+denoiser.py's ``Denoiser``) as native HIP passes.
+
+    wg = load_waveglow("waveglow.pt").cuda().eval()
+    audio = wg.infer(mel, sigma=0.666)                 # (B, 256 * N) float32
+    clean = Denoiser(wg)(audio, strength=0.01)         # (B, 1, T)
+
+The module keeps NVIDIA's submodule names (after ``remove_weightnorm``), so ``state_dict()`` keys match glow.py.  Its
+weights are f32 masters; ``precision`` selects the compute of the products: 'fp32' (exact f32 MFMA), 'bf16x3'
+(split-bf16, three products) or 'bf16'.  ``.half()`` keeps the f32 weights, selects 'bf16' and makes ``infer`` return
+float16; ``.float()`` goes back to 'fp32'.
+
+Per call: one upsample product per utterance, then per flow one cond product (t2amd_gemm_f32), two WN layer products per
+layer (t2amd_wg_layer_f32: the gated dilated product and the residual / skip product) and one flow tail
+(t2amd_wg_tail_f32: end, affine inverse, inverse 1x1 mix, noise insertion and the next flow's start).  All buffers are
+allocated once per call, before the flow loop, which does no allocation, copy or host synchronisation.
+The arithmetic is restated in float64 torch by tests/waveglow_ref.py; DESIGN.md section 10 has the layout.
+"""
+import numpy as np
+import torch
+from torch import nn
+
+from . import native as nv
+from .audio import STFT
+
+PRECISIONS = {'fp32': 0, 'bf16x3': 1, 'bf16': 2}
+HOP = 256                    # upsample stride (NVIDIA's ConvTranspose1d(n_mel, n_mel, 1024, stride=256))
+UP_KERNEL = 1024
+
+
+def fold_weight_norm(state_dict):
+    """Replace every ``X.weight_g`` / ``X.weight_v`` pair by ``X.weight = g * v / ||v||`` (norm over all dims but 0),
+    computed as ``torch.nn.utils.remove_weight_norm`` does."""
+    out = {}
+    for k, v in state_dict.items():
+        if k.endswith('.weight_v'):
+            continue
+        if k.endswith('.weight_g'):
+            base = k[:-len('_g')]
+            out[base] = torch._weight_norm(state_dict[base + '_v'], v, 0).detach()
+        else:
+            out[k] = v
+    return out
+
+
+def config_from_state_dict(state_dict):
+    """WaveGlow constructor arguments from the tensor shapes of a (folded or weight-normed) state dict."""
+    sd = state_dict
+    legacy = [k for k in sd if '.cond_layers.' in k or '.res_layers.' in k or '.skip_layers.' in k]
+    if legacy:
+        raise ValueError("WaveGlow: this is the pre-2019 checkpoint layout (per-layer cond_layers, separate res_layers / "
+                         "skip_layers, e.g. %s); convert it with NVIDIA's convert_model.py first" % legacy[0])
+
+    def w(name):
+        for suffix in ('.weight', '.weight_v'):
+            if name + suffix in sd:
+                return sd[name + suffix]
+        raise KeyError("WaveGlow: missing %s.weight" % name)
+
+    flows = sorted({int(k.split('.')[1]) for k in sd if k.startswith('WN.')})
+    if not flows or flows != list(range(len(flows))):
+        raise ValueError("WaveGlow: no WN.<k> flows in the state dict")
+    n_flows = len(flows)
+    n_mel = w('upsample').shape[0]
+    C = w('WN.0.start').shape[0]
+    L = len({k.split('.')[3] for k in sd if k.startswith('WN.0.in_layers.')})
+    ks = w('WN.0.in_layers.0').shape[2]
+    chans = [w('convinv.%d.conv' % k).shape[0] for k in range(n_flows)]
+    n_group = chans[0]
+    every, size = n_flows, 0
+    for k in range(1, n_flows):
+        if chans[k] != chans[0]:
+            every, size = k, chans[0] - chans[k]
+            break
+    cfg = dict(n_mel_channels=n_mel, n_flows=n_flows, n_group=n_group, n_early_every=every, n_early_size=size,
+               WN_config=dict(n_layers=L, n_channels=C, kernel_size=ks))
+    want, c = [], n_group
+    for k in range(n_flows):
+        if k % every == 0 and k > 0:
+            c -= size
+        want.append(c)
+    if want != chans:
+        raise ValueError("WaveGlow: per-flow channel counts %s follow no (n_early_every, n_early_size)" % chans)
+    return cfg
+
+
+class Invertible1x1Conv(nn.Module):
+    """glow.py's Invertible1x1Conv: a bias-free 1x1 conv with an orthonormal, det = +1 initial weight.  Only the
+    inverse is used at inference (computed once per weight version in float64, see WaveGlow._packed)."""
+
+    def __init__(self, c):
+        super().__init__()
+        self.conv = nn.Conv1d(c, c, kernel_size=1, stride=1, padding=0, bias=False)
+        W = torch.linalg.qr(torch.randn(c, c))[0]
+        if torch.det(W) < 0:
+            W[:, 0] = -W[:, 0]
+        self.conv.weight.data = W.view(c, c, 1)
+
+
+class WN(nn.Module):
+    """glow.py's WN (the fused-cond form): start, in_layers, res_skip_layers, cond_layer, end."""
+
+    def __init__(self, n_in_channels, n_mel_channels, n_layers, n_channels, kernel_size):
+        super().__init__()
+        self.n_layers, self.n_channels = n_layers, n_channels
+        self.in_layers = nn.ModuleList()
+        self.res_skip_layers = nn.ModuleList()
+        self.start = nn.Conv1d(n_in_channels, n_channels, 1)
+        self.end = nn.Conv1d(n_channels, 2 * n_in_channels, 1)
+        self.end.weight.data.zero_()                  # NVIDIA's init: every affine coupling starts as the identity
+        self.end.bias.data.zero_()
+        self.cond_layer = nn.Conv1d(n_mel_channels, 2 * n_channels * n_layers, 1)
+        for i in range(n_layers):
+            d = 2 ** i
+            self.in_layers.append(nn.Conv1d(n_channels, 2 * n_channels, kernel_size, dilation=d,
+                                            padding=(kernel_size * d - d) // 2))
+            self.res_skip_layers.append(nn.Conv1d(n_channels, 2 * n_channels if i < n_layers - 1 else n_channels, 1))
+
+
+class WaveGlow(nn.Module):
+    def __init__(self, n_mel_channels, n_flows, n_group, n_early_every, n_early_size, WN_config, precision='fp32'):
+        super().__init__()
+        C, L, ks = WN_config['n_channels'], WN_config['n_layers'], WN_config['kernel_size']
+        if ks != 3:
+            raise ValueError("WaveGlow: kernel_size %d is not supported (the native path is kernel 3)" % ks)
+        if n_group % 2:
+            raise ValueError("WaveGlow: n_group must be even, got %d" % n_group)
+        if n_group > 16 or HOP % n_group:
+            raise ValueError("WaveGlow: n_group must divide %d and be at most 16, got %d" % (HOP, n_group))
+        if C % 64 or C > 512:
+            raise ValueError("WaveGlow: n_channels must be a multiple of 64 up to 512, got %d" % C)
+        if n_early_size % 2:
+            raise ValueError("WaveGlow: n_early_size must be even, got %d" % n_early_size)
+        if n_mel_channels % 16:
+            raise ValueError("WaveGlow: n_mel_channels must be a multiple of 16, got %d" % n_mel_channels)
+        self.n_mel_channels, self.n_flows, self.n_group = n_mel_channels, n_flows, n_group
+        self.n_early_every, self.n_early_size = n_early_every, n_early_size
+        self.n_layers, self.n_channels = L, C
+        self.upsample = nn.ConvTranspose1d(n_mel_channels, n_mel_channels, UP_KERNEL, stride=HOP)
+        self.WN = nn.ModuleList()
+        self.convinv = nn.ModuleList()
+        n_half, n_rem = n_group // 2, n_group
+        self.flow_channels = []
+        for k in range(n_flows):
+            if k % n_early_every == 0 and k > 0:
+                n_half -= n_early_size // 2
+                n_rem -= n_early_size
+            if n_rem < 2:
+                raise ValueError("WaveGlow: the early outputs leave %d channels" % n_rem)
+            self.convinv.append(Invertible1x1Conv(n_rem))
+            self.WN.append(WN(n_half, n_mel_channels * n_group, **WN_config))
+            self.flow_channels.append(n_rem)
+        self.n_remaining_channels = n_rem
+        self.precision = precision
+        self.half_io = False
+        self._pack = None
+
+    # ---- precision / dtype -------------------------------------------------------------------------------------------
+    @property
+    def precision(self):
+        return self._precision
+
+    @precision.setter
+    def precision(self, p):
+        if p not in PRECISIONS:
+            raise ValueError("WaveGlow: precision must be one of %s, got %r" % (sorted(PRECISIONS), p))
+        self._precision = p
+
+    def half(self):
+        """f32 master weights kept; bf16 compute, float16 output."""
+        self.precision, self.half_io = 'bf16', True
+        return self
+
+    def float(self):
+        super().float()
+        self.precision, self.half_io = 'fp32', False
+        return self
+
+    # ---- loading ------------------------------------------------------------------------------------------------------
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        sd = fold_weight_norm(dict(state_dict))
+        cfg = config_from_state_dict(sd)
+        mine = dict(n_mel_channels=self.n_mel_channels, n_flows=self.n_flows, n_group=self.n_group,
+                    WN_config=dict(n_layers=self.n_layers, n_channels=self.n_channels, kernel_size=3))
+        got = {k: cfg[k] for k in mine}
+        if got != mine:
+            raise ValueError("WaveGlow: state dict geometry %s does not match the module's %s" % (got, mine))
+        sd = {k: v.float() if torch.is_tensor(v) and v.is_floating_point() else v for k, v in sd.items()}
+        self._pack = None
+        return super().load_state_dict(sd, strict=strict, assign=assign)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, precision='fp32'):
+        sd = fold_weight_norm(dict(state_dict))
+        m = cls(precision=precision, **config_from_state_dict(sd))
+        m.load_state_dict(sd)
+        return m
+
+    @classmethod
+    def from_module(cls, module, precision='fp32'):
+        """Adopt a loaded NVIDIA WaveGlow (weight-normed or not): its weights are read once."""
+        with torch.no_grad():
+            sd = {k: v.detach().float().cpu() for k, v in module.state_dict().items()}
+        return cls.from_state_dict(sd, precision=precision)
+
+    # ---- device-side weight layout ------------------------------------------------------------------------------------
+    def _packed(self, device):
+        key = (str(device), tuple((p.data_ptr(), p._version) for p in self.parameters()))
+        if self._pack is not None and self._pack[0] == key:
+            return self._pack[1]
+        C, L, G, nm = self.n_channels, self.n_layers, self.n_group, self.n_mel_channels
+        taps = UP_KERNEL // HOP
+        with torch.no_grad():
+            # upsample: out[q][p n_mel + co] = sum_{j, ci} x[q - j][ci] W[ci][co][p + 256 j]  (B operand [N][K], K = (j, ci))
+            W = self.upsample.weight.detach().float().view(nm, nm, taps, HOP)
+            up_w = W.permute(3, 1, 2, 0).reshape(HOP * nm, taps * nm).contiguous()
+            up_b = self.upsample.bias.detach().float().repeat(HOP).contiguous()
+            # gate packing: block 64 q + [0, 32) = tanh channels 32 q + [0, 32), block 64 q + [32, 64) their partners
+            q = torch.arange(C // 32).view(-1, 1, 1)
+            half = torch.arange(2).view(1, -1, 1)
+            j = torch.arange(32).view(1, 1, -1)
+            gate_perm = (half * C + 32 * q + j).reshape(-1).to(device)
+            flows = []
+            for k in range(self.n_flows):
+                wn = self.WN[k]
+                f = {}
+                cw = wn.cond_layer.weight.detach().float().view(2 * C * L, nm, G)
+                f['cond_w'] = cw.permute(0, 2, 1).reshape(2 * C * L, G * nm).contiguous()     # column g n_mel + c
+                f['cond_b'] = wn.cond_layer.bias.detach().float().contiguous()
+                f['in_w'], f['in_b'], f['rs_w'], f['rs_b'] = [], [], [], []
+                for i in range(L):
+                    iw = wn.in_layers[i].weight.detach().float().permute(0, 2, 1).reshape(2 * C, 3 * C)
+                    f['in_w'].append(iw.index_select(0, gate_perm).contiguous())
+                    f['in_b'].append(wn.in_layers[i].bias.detach().float().index_select(0, gate_perm).contiguous())
+                    rw = wn.res_skip_layers[i].weight.detach().float()
+                    f['rs_w'].append(rw.view(rw.shape[0], C).contiguous())
+                    f['rs_b'].append(wn.res_skip_layers[i].bias.detach().float().contiguous())
+                sw = wn.start.weight.detach().float()
+                f['start_w'] = sw.view(C, sw.shape[1]).contiguous()
+                f['start_b'] = wn.start.bias.detach().float().contiguous()
+                ew = wn.end.weight.detach().float()
+                f['end_w'] = ew.view(ew.shape[0], C).contiguous()
+                f['end_b'] = wn.end.bias.detach().float().contiguous()
+                wc = self.convinv[k].conv.weight.detach()
+                f['winv'] = torch.linalg.inv(wc.double().cpu().view(wc.shape[0], wc.shape[0])).float().contiguous().to(device)
+                flows.append(f)
+        pk = dict(up_w=up_w, up_b=up_b, flows=flows)
+        self._pack = (key, pk)
+        return pk
+
+    # ---- inference ----------------------------------------------------------------------------------------------------
+    def halo(self):
+        return 2 ** (self.n_layers - 1)            # (kernel_size - 1) / 2 * the deepest dilation
+
+    def noise_shapes(self, B, N):
+        """Shapes of the noise tensors infer draws, in draw order (reference: FloatTensor(...).normal_())."""
+        R = HOP * N // self.n_group
+        shapes = [(B, self.n_remaining_channels, R)]
+        for k in reversed(range(self.n_flows)):
+            if k % self.n_early_every == 0 and k > 0:
+                shapes.append((B, self.n_early_size, R))
+        return shapes
+
+    def packed_plan(self, lengths):
+        """(rowb, rowr, offsets, P) of the packed row space for per-utterance frame counts `lengths` (host tensors)."""
+        H, spf = self.halo(), HOP // self.n_group
+        rowb, rowr, offs = [np.full(H, -1, np.int32)], [np.zeros(H, np.int32)], []
+        pos = H
+        for b, n in enumerate(lengths):
+            R = spf * int(n)
+            offs.append(pos)
+            rowb += [np.full(R, b, np.int32), np.full(H, -1, np.int32)]
+            rowr += [np.arange(R, dtype=np.int32), np.zeros(H, np.int32)]
+            pos += R + H
+        return torch.from_numpy(np.concatenate(rowb)), torch.from_numpy(np.concatenate(rowr)), offs, pos
+
+    @torch.no_grad()
+    def infer(self, spect, sigma=1.0, lengths=None, z=None):
+        """(B, n_mel, N) mels (float32 / float16 / bfloat16) -> (B, 256 N) audio (float16 after ``.half()``).
+        ``lengths``: frames per utterance (ragged: each computed as if alone, zero beyond 256 n_b); ``z``: the noise
+        tensors in ``noise_shapes`` order instead of drawing them."""
+        dev = self.upsample.weight.device
+        if dev.type != 'cuda' and not nv.validate_only():
+            raise nv.NativeError("WaveGlow: move the module to the MI355X first (.cuda()); there is no CPU path")
+        if spect.dim() != 3 or spect.shape[1] != self.n_mel_channels:
+            raise ValueError("WaveGlow.infer: expected (B, %d, N) mels, got %s" % (self.n_mel_channels, tuple(spect.shape)))
+        if spect.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError("WaveGlow.infer: mels must be float32, float16 or bfloat16, got %s" % spect.dtype)
+        B, nm, N = spect.shape
+        lens = [N] * B if lengths is None else [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if len(lens) != B or min(lens) < 1 or max(lens) > N:
+            raise ValueError("WaveGlow.infer: lengths %s do not fit %d utterances of %d frames" % (lens, B, N))
+        shapes = self.noise_shapes(B, N)
+        if z is None:
+            z = [torch.empty(s, dtype=torch.float32, device=dev).normal_() for s in shapes]
+        else:
+            z = list(z)
+            if [tuple(t.shape) for t in z] != shapes:
+                raise ValueError("WaveGlow.infer: noise shapes %s, expected %s" % ([tuple(t.shape) for t in z], shapes))
+            z = [t.to(device=dev, dtype=torch.float32).contiguous() for t in z]
+        prec = PRECISIONS[self.precision]
+        pk = self._packed(dev)
+        C, L, G, H = self.n_channels, self.n_layers, self.n_group, self.halo()
+        rowb, rowr, offs, P = self.packed_plan(lens)
+        rowb, rowr = rowb.to(dev), rowr.to(dev)
+        mel = spect.to(device=dev, dtype=torch.float32).contiguous()
+
+        # one workspace: cond_g [P][G n_mel] | cnd [P][2CL] | h, acts, skip [P][C] | audio [P][G] | mel_cl [B N][n_mel]
+        sizes = [P * G * nm, P * 2 * C * L, P * C, P * C, P * C, P * G, B * N * nm]
+        ws = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        parts, o = [], 0
+        for s in sizes:
+            parts.append(ws[o:o + s])
+            o += s
+        cond_g = parts[0].view(P, G * nm)
+        cnd = parts[1].view(P, 2 * C * L)
+        h, acts, skip = (t.view(P, C) for t in parts[2:5])
+        audio = parts[5].view(P, G)
+        mel_cl = parts[6].view(B * N, nm)
+        cond_g.zero_()
+        h.zero_()
+        out = torch.zeros(B, HOP * N, dtype=torch.float32, device=dev)
+
+        # upsample + grouping: one implicit-conv product per utterance, rows straight into the packed space
+        nv.transpose(mel_cl[:N], mel[0], batch=B, sstride=nm * N, dstride=N * nm)
+        taps = UP_KERNEL // HOP
+        spf = HOP // G
+        for b, n in enumerate(lens):
+            dst = cond_g[offs[b]:offs[b] + spf * n].view(n, HOP * nm)
+            nv.gemm(dst, mel_cl[b * N:b * N + n], pk['up_w'], bias=pk['up_b'], convA=(n, nm, 0, -1), fast=prec)
+
+        rows = slice(H, P - H)
+        cond_r, cnd_r, h_r, acts_r, skip_r, rowb_r = cond_g[rows], cnd[rows], h[rows], acts[rows], skip[rows], rowb[rows]
+        fl = pk['flows']
+        nv.wg_tail(rowb, rowr, audio, G, z=z[0], sigma=sigma, start_w=fl[-1]['start_w'], start_b=fl[-1]['start_b'], h=h)
+        zi = 1
+        for k in reversed(range(self.n_flows)):
+            f = fl[k]
+            nv.gemm(cnd_r, cond_r, f['cond_w'], bias=f['cond_b'], fast=prec)
+            for i in range(L):
+                nv.wg_gated(h_r, f['in_w'][i], f['in_b'][i], 2 ** i, cnd_r[:, 2 * C * i:2 * C * (i + 1)], acts_r, prec)
+                last = i == L - 1
+                nv.wg_res_skip(acts_r, f['rs_w'][i], f['rs_b'][i], None if last else h_r, skip_r, i == 0, rowb_r, prec)
+            early = k % self.n_early_every == 0 and k > 0
+            nxt = fl[k - 1] if k > 0 else None
+            nv.wg_tail(rowb, rowr, audio, G, skip=skip, end_w=f['end_w'], end_b=f['end_b'], winv=f['winv'],
+                       z=z[zi] if early else None, sigma=sigma,
+                       start_w=nxt['start_w'] if nxt else None, start_b=nxt['start_b'] if nxt else None,
+                       h=h if nxt else None, out=out if k == 0 else None)
+            zi += 1 if early else 0
+        return out.half() if self.half_io else out
+
+
+class Denoiser(nn.Module):
+    """denoiser.py: removes the model bias (the audio of a silent mel) from the magnitude spectrum."""
+
+    def __init__(self, waveglow, filter_length=1024, n_overlap=4, win_length=1024, mode='zeros'):
+        super().__init__()
+        dev = waveglow.upsample.weight.device
+        self.stft = STFT(filter_length=filter_length, hop_length=int(filter_length / n_overlap),
+                         win_length=win_length).to(dev)
+        if mode == 'zeros':
+            mel_input = torch.zeros((1, 80, 88), dtype=torch.float32, device=dev)
+        elif mode == 'normal':
+            mel_input = torch.randn((1, 80, 88), dtype=torch.float32, device=dev)
+        else:
+            raise Exception("Mode {} if not supported".format(mode))
+        with torch.no_grad():
+            bias_audio = waveglow.infer(mel_input, sigma=0.0).float()
+            bias_spec, _ = self.stft.transform(bias_audio)
+        self.register_buffer('bias_spec', bias_spec[:, :, 0][:, :, None].contiguous())
+
+    def forward(self, audio, strength=0.1):
+        audio_spec, audio_angles = self.stft.transform(audio.float())
+        nv.wg_denoise(audio_spec, self.bias_spec, strength)
+        return self.stft.inverse(audio_spec, audio_angles)
+
+
+def load_waveglow(src, precision='fp32'):
+    """A WaveGlow from a checkpoint path, a state dict, ``{'model': state dict or module}`` or a module."""
+    if isinstance(src, str):
+        src = torch.load(src, map_location='cpu', weights_only=False)
+    if isinstance(src, dict) and 'model' in src:
+        src = src['model']
+    if isinstance(src, WaveGlow):
+        return src
+    if isinstance(src, nn.Module):
+        return WaveGlow.from_module(src, precision=precision)
+    if isinstance(src, dict):
+        return WaveGlow.from_state_dict(src, precision=precision)
+    raise TypeError("load_waveglow: expected a path, a state dict or a module, got %s" % type(src).__name__)
