@@ -980,6 +980,32 @@ int t2amd_wg_tail_f32(const float* skip, long long ldskip, int C, const float* e
 int t2amd_wg_denoise_f32(float* mag, const float* bias, int B, int F, long long n, float strength, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * WaveGlow forward direction (csrc/waveglow_fwd.hip; WaveGlow.forward / WaveGlow.nll / WaveGlowLoss): audio to latents and
+ * the terms of the negative log-likelihood.  The products are the ones inference runs; the packed row space is the same.
+ * ------------------------------------------------------------------------------------ */
+/* Flow head over P packed rows (rows with 0 <= rowb < B and rowr < R; b = rowb[p], r = rowr[p]), f32.  It closes one flow
+ * and opens the next:
+ *   x = audio[p][0:n_in];  e = end_b + end_w[n_in][C] . skip[p];  x1 = exp(e[n_in/2:]) * x1 + e[:n_in/2];
+ *   log_s[b*lsb + j*lsc + r] = e[n_in/2 + j]   (end_w NULL, the first call: x[g] = wave[b*ldwave + n_group*r + g], all
+ *   n_group channels, and no flow to close; exactly one of end_w / wave is set);
+ *   z[b*zb + (z_off + k)*zc + r] = x[k] for k < n_emit (an early output; on the last call every channel that is left);
+ *   a = mix_w[n_out][n_out] . x[n_emit:], n_out = n_in - n_emit;  audio[p][0:n_out] = a;
+ *   h[p][c] = start_b[c] + start_w[c][0:n_out/2] . a   (mix_w NULL: the last call, n_emit == n_in, nothing to open).
+ * R bounds the rows of one utterance (lsc, zc >= R).  C <= 512, even n_group <= 16. */
+int t2amd_wg_head_f32(const float* skip, long long ldskip, int C, const float* end_w, const float* end_b, int n_in,
+                      float* log_s, long long lsb, long long lsc, const float* wave, long long ldwave, float* audio,
+                      long long ldaudio, float* z, long long zb, long long zc, int z_off, int n_emit, const float* mix_w,
+                      const float* start_w, const float* start_b, float* h, long long ldh, const int* rowb,
+                      const int* rowr, long long P, int n_group, int B, long long R, void* stream);
+/* out[b][0] = sum over c < nz, r < len[b] of z[b*zb + c*zc + r]^2 and out[b][1] = the same sum of ls[b*lb + c*lc + r]
+ * over c < nls (ls NULL with nls 0: 0), in double and in a fixed order (two launches, no atomics): an utterance's sums do
+ * not depend on the batch it sits in.  len (device) is clamped to [0, R]; partial holds B * nchunk * 2 doubles with
+ * nchunk = ceil(R / t2amd_wg_nll_chunk()). */
+int t2amd_wg_nll_chunk(void);
+int t2amd_wg_nll_f32(const float* z, long long zb, long long zc, int nz, const float* ls, long long lb, long long lc, int nls,
+                     const int* len, int B, long long R, double* partial, long long nchunk, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Optimiser step: global-norm clipping + Adam over all parameter
  * tensors in two launches.  Replaces reference train.py:233-236
  *   grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), grad_clip_thresh)

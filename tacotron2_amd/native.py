@@ -287,7 +287,7 @@ SYMBOLS = [
     "t2amd_reflect_pad_f32", "t2amd_reflect_index", "t2amd_stft_magnitude_f32", "t2amd_mel_log_compress_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
-    "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32",
+    "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
     "t2amd_optim_chunk", "t2amd_grad_norm_f32", "t2amd_adam_step_f32",
     "t2amd_decoder_persist_mailbox_bytes", "t2amd_decoder_persist_supported", "t2amd_decoder_infer_persistent_f32",
     "t2amd_loss_workspace_doubles", "t2amd_tacotron2_loss_fwd_f32", "t2amd_tacotron2_loss_bwd_f32",
@@ -391,6 +391,10 @@ def _argtypes():
         "t2amd_wg_tail_f32": [_P, _L, _I, _P, _P, _I, _P, _P, _L, _P, _L, _L, _I, _F, _P, _P, _P, _L, _P, _L, _P, _P, _L,
                               _I, _P],
         "t2amd_wg_denoise_f32": [_P, _P, _I, _I, _L, _F, _P],
+        "t2amd_wg_head_f32": [_P, _L, _I, _P, _P, _I, _P, _L, _L, _P, _L, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _L, _P,
+                              _P, _L, _I, _I, _L, _P],
+        "t2amd_wg_nll_chunk": [],
+        "t2amd_wg_nll_f32": [_P, _L, _L, _I, _P, _L, _L, _I, _P, _I, _L, _P, _L, _P, _P],
         "t2amd_optim_chunk": [],
         "t2amd_grad_norm_f32": [pt(TensorList), _F, _P, _P, _P],
         "t2amd_adam_step_f32": [pt(TensorList), pt(AdamHyper), _P, _P],
@@ -1755,6 +1759,85 @@ def wg_denoise(mag, bias, strength):
         raise NativeError("wg_denoise: bias has %d entries for %d bins" % (bias.numel(), F))
     _check(load().t2amd_wg_denoise_f32(ptr(_fullc(mag)), ptr(_fullc(bias)), B, F, _i64(n), _F(strength), _stream()),
            "t2amd_wg_denoise_f32")
+
+
+# ----------------------------------------------------------------------------
+# WaveGlow forward direction (csrc/waveglow_fwd.hip)
+# ----------------------------------------------------------------------------
+def _chan_rows(t, what, dtype=torch.float32):
+    """(B, c, R) tensor with unit row stride -> (ptr, batch stride, channel stride, c, R)."""
+    if t.dim() != 3 or (t.shape[2] > 1 and t.stride(2) != 1):
+        raise NativeError("%s: expected a (B, channels, rows) tensor with contiguous rows, got shape %s stride %s"
+                          % (what, tuple(t.shape), t.stride()))
+    return ptr(t, dtype), t.stride(0), t.stride(1), t.shape[1], t.shape[2]
+
+
+def wg_head(rowb, rowr, audio, n_group, B, R, skip=None, end_w=None, end_b=None, log_s=None, wave=None, z=None, z_off=0,
+            n_emit=0, mix_w=None, start_w=None, start_b=None, h=None):
+    """The flow head over every packed row (see the header).  log_s (B, n_in / 2, R) and z (B, n_group, R) with contiguous
+    rows (any batch / channel stride); wave (B, >= n_group R) waveform rows; end_w (n_in, C), mix_w (n_out, n_out) and
+    start_w (C, n_out / 2) contiguous."""
+    P = rowb.numel()
+    pa, lda, Pa, _ = _mat(audio)
+    if Pa != P or rowr.numel() != P:
+        raise NativeError("wg_head: %d audio rows / %d rowr for %d packed rows" % (Pa, rowr.numel(), P))
+    n_in, nc = (end_w.shape[0], end_w.shape[1]) if end_w is not None else (0, 0)
+    ps, lds = None, 0
+    if skip is not None:
+        ps, lds, _, cs = _mat(skip)
+        nc = nc or cs
+    if start_w is not None:
+        nc = nc or start_w.shape[0]
+    ph, ldh = None, 0
+    if h is not None:
+        ph, ldh, _, ch = _mat(h)
+        nc = nc or ch
+    pl, lsb, lsc = None, 0, 0
+    if log_s is not None:
+        pl, lsb, lsc, nl, Rl = _chan_rows(log_s, "wg_head: log_s")
+        if (nl, Rl, log_s.shape[0]) != (n_in // 2, R, B):
+            raise NativeError("wg_head: log_s %s for B=%d, n_in=%d, R=%d" % (tuple(log_s.shape), B, n_in, R))
+    pz, zb, zc = None, 0, 0
+    if z is not None:
+        pz, zb, zc, nz, Rz = _chan_rows(z, "wg_head: z")
+        if (nz, Rz, z.shape[0]) != (n_group, R, B):
+            raise NativeError("wg_head: z %s for B=%d, n_group=%d, R=%d" % (tuple(z.shape), B, n_group, R))
+    pw, ldw = None, 0
+    if wave is not None:
+        pw, ldw, Bw, _ = _mat(wave)
+        if Bw != B:
+            raise NativeError("wg_head: %d waveforms for B=%d" % (Bw, B))
+    if mix_w is not None and (mix_w.dim() != 2 or mix_w.shape[0] != mix_w.shape[1] or start_w is None
+                              or start_w.dim() != 2 or 2 * start_w.shape[1] != mix_w.shape[0]):
+        raise NativeError("wg_head: mix_w (n, n) needs start_w (C, n / 2)")
+    _check(load().t2amd_wg_head_f32(ps, _i64(lds), int(nc), _opt(end_w), _opt(end_b), int(n_in), pl, _i64(lsb), _i64(lsc),
+                                    pw, _i64(ldw), pa, _i64(lda), pz, _i64(zb), _i64(zc), int(z_off), int(n_emit),
+                                    _opt(mix_w), _opt(start_w), _opt(start_b), ph, _i64(ldh), ptr(rowb, torch.int32),
+                                    ptr(rowr, torch.int32), _i64(P), int(n_group), int(B), _i64(R), _stream()),
+           "t2amd_wg_head_f32")
+
+
+def wg_nll_chunk():
+    return int(load().t2amd_wg_nll_chunk())
+
+
+def wg_nll(z, log_s, rows, partial, out):
+    """out (B, 2) float64 = per utterance {sum z^2, sum log_s} over the first rows[b] (device int32) rows of z (B, c, R) and
+    log_s (B, c', R) (None: 0), rows contiguous.  partial: float64 workspace, >= B * ceil(R / wg_nll_chunk()) * 2."""
+    pz, zb, zc, nz, R = _chan_rows(z, "wg_nll: z")
+    B = z.shape[0]
+    pl, lb, lc, nls = None, 0, 0, 0
+    if log_s is not None:
+        pl, lb, lc, nls, Rl = _chan_rows(log_s, "wg_nll: log_s")
+        if Rl != R or log_s.shape[0] != B:
+            raise NativeError("wg_nll: log_s %s beside z %s" % (tuple(log_s.shape), tuple(z.shape)))
+    nchunk = (R + wg_nll_chunk() - 1) // wg_nll_chunk()
+    if rows.numel() != B or partial.numel() < B * nchunk * 2 or out.numel() != 2 * B:
+        raise NativeError("wg_nll: %d row counts, %d partials, %d outputs for B=%d, R=%d" % (rows.numel(), partial.numel(),
+                                                                                           out.numel(), B, R))
+    _check(load().t2amd_wg_nll_f32(pz, _i64(zb), _i64(zc), int(nz), pl, _i64(lb), _i64(lc), int(nls), ptr(rows, torch.int32),
+                                   int(B), _i64(R), ptr(_fullc(partial), torch.float64), _i64(nchunk),
+                                   ptr(_fullc(out), torch.float64), _stream()), "t2amd_wg_nll_f32")
 
 
 # ----------------------------------------------------------------------------

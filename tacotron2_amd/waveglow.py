@@ -4,6 +4,8 @@ denoiser.py's ``Denoiser``) as native HIP passes.
     wg = load_waveglow("waveglow.pt").cuda().eval()
     audio = wg.infer(mel, sigma=0.666)                 # (B, 256 * N) float32
     clean = Denoiser(wg)(audio, strength=0.01)         # (B, 1, T)
+    z, log_s_list, log_det_W_list = wg((mel, audio))   # glow.py's forward: audio -> latents (no backward pass)
+    nats = wg.nll(mel, audio, sigma=1.0)               # (B,) negative log-likelihood per sample, per utterance
 
 The module keeps NVIDIA's submodule names (after ``remove_weightnorm``), so ``state_dict()`` keys match glow.py.  Its
 weights are f32 masters; ``precision`` selects the compute of the products: 'fp32' (exact f32 MFMA), 'bf16x3'
@@ -14,8 +16,13 @@ Per call: one upsample product per utterance, then per flow one cond product (t2
 layer (t2amd_wg_layer_f32: the gated dilated product and the residual / skip product) and one flow tail
 (t2amd_wg_tail_f32: end, affine inverse, inverse 1x1 mix, noise insertion and the next flow's start).  All buffers are
 allocated once per call, before the flow loop, which does no allocation, copy or host synchronisation.
-The arithmetic is restated in float64 torch by tests/waveglow_ref.py; DESIGN.md section 10 has the layout.
+The forward direction (``forward``, ``nll``, ``WaveGlowLoss``) runs the same products; between them one flow head per
+flow boundary (t2amd_wg_head_f32: end, affine coupling, log_s, early output, the next flow's 1x1 mix and start) and, for
+the loss, one fixed-order reduction (t2amd_wg_nll_f32).  It has no backward pass: its outputs do not require grad.
+The arithmetic is restated in float64 torch by tests/waveglow_ref.py and tests/waveglow_fwd_ref.py; DESIGN.md section 10
+has the layout.
 """
+
 import numpy as np
 import torch
 from torch import nn
@@ -220,7 +227,7 @@ class WaveGlow(nn.Module):
             half = torch.arange(2).view(1, -1, 1)
             j = torch.arange(32).view(1, 1, -1)
             gate_perm = (half * C + 32 * q + j).reshape(-1).to(device)
-            flows = []
+            flows, logdet = [], []
             for k in range(self.n_flows):
                 wn = self.WN[k]
                 f = {}
@@ -243,8 +250,13 @@ class WaveGlow(nn.Module):
                 f['end_b'] = wn.end.bias.detach().float().contiguous()
                 wc = self.convinv[k].conv.weight.detach()
                 f['winv'] = torch.linalg.inv(wc.double().cpu().view(wc.shape[0], wc.shape[0])).float().contiguous().to(device)
+                # the forward direction: the weight itself and log det W (float64 on the host; nan when det W < 0, as
+                # torch.logdet gives)
+                f['mix_w'] = wc.float().view(wc.shape[0], wc.shape[0]).contiguous()
+                sign, logabs = torch.linalg.slogdet(wc.double().cpu().view(wc.shape[0], wc.shape[0]))
+                logdet.append(float(logabs) if float(sign) > 0 else (float('-inf') if float(sign) == 0 else float('nan')))
                 flows.append(f)
-        pk = dict(up_w=up_w, up_b=up_b, flows=flows)
+        pk = dict(up_w=up_w, up_b=up_b, flows=flows, logdet=logdet)
         self._pack = (key, pk)
         return pk
 
@@ -273,6 +285,25 @@ class WaveGlow(nn.Module):
             rowr += [np.arange(R, dtype=np.int32), np.zeros(H, np.int32)]
             pos += R + H
         return torch.from_numpy(np.concatenate(rowb)), torch.from_numpy(np.concatenate(rowr)), offs, pos
+
+    def _workspace(self, P, B, N, dev):
+        """One allocation per call: cond_g [P][G n_mel] (zeroed) | cnd [P][2CL] | h (zeroed), acts, skip [P][C] |
+        audio [P][G] | mel_cl [B N][n_mel]."""
+        C, L, G, nm = self.n_channels, self.n_layers, self.n_group, self.n_mel_channels
+        sizes = [P * G * nm, P * 2 * C * L, P * C, P * C, P * C, P * G, B * N * nm]
+        ws = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        parts, o = [], 0
+        for s in sizes:
+            parts.append(ws[o:o + s])
+            o += s
+        cond_g = parts[0].view(P, G * nm)
+        cnd = parts[1].view(P, 2 * C * L)
+        h, acts, skip = (t.view(P, C) for t in parts[2:5])
+        audio = parts[5].view(P, G)
+        mel_cl = parts[6].view(B * N, nm)
+        cond_g.zero_()
+        h.zero_()
+        return cond_g, cnd, h, acts, skip, audio, mel_cl
 
     @torch.no_grad()
     def infer(self, spect, sigma=1.0, lengths=None, z=None):
@@ -305,20 +336,7 @@ class WaveGlow(nn.Module):
         rowb, rowr = rowb.to(dev), rowr.to(dev)
         mel = spect.to(device=dev, dtype=torch.float32).contiguous()
 
-        # one workspace: cond_g [P][G n_mel] | cnd [P][2CL] | h, acts, skip [P][C] | audio [P][G] | mel_cl [B N][n_mel]
-        sizes = [P * G * nm, P * 2 * C * L, P * C, P * C, P * C, P * G, B * N * nm]
-        ws = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-        parts, o = [], 0
-        for s in sizes:
-            parts.append(ws[o:o + s])
-            o += s
-        cond_g = parts[0].view(P, G * nm)
-        cnd = parts[1].view(P, 2 * C * L)
-        h, acts, skip = (t.view(P, C) for t in parts[2:5])
-        audio = parts[5].view(P, G)
-        mel_cl = parts[6].view(B * N, nm)
-        cond_g.zero_()
-        h.zero_()
+        cond_g, cnd, h, acts, skip, audio, mel_cl = self._workspace(P, B, N, dev)
         out = torch.zeros(B, HOP * N, dtype=torch.float32, device=dev)
 
         # upsample + grouping: one implicit-conv product per utterance, rows straight into the packed space
@@ -349,6 +367,217 @@ class WaveGlow(nn.Module):
                        h=h if nxt else None, out=out if k == 0 else None)
             zi += 1 if early else 0
         return out.half() if self.half_io else out
+
+
+    # ---- forward direction: audio -> latents ----------------------------------------------------------------------------
+    def early_outputs(self):
+        """The flows k > 0 that are preceded by an early output."""
+        return [k for k in range(1, self.n_flows) if k % self.n_early_every == 0]
+
+    def latents_to_noise(self, z):
+        """(B, n_group, T') latents of ``forward`` -> the noise list ``infer(z=...)`` takes (``noise_shapes`` order): the
+        remaining channels first, then the early outputs in reverse order."""
+        E, n_e = self.n_early_size, len(self.early_outputs())
+        return [z[:, E * n_e:]] + [z[:, E * i:E * (i + 1)] for i in reversed(range(n_e))]
+
+    def noise_to_latents(self, noise):
+        """The inverse of ``latents_to_noise``."""
+        noise = list(noise)
+        if len(noise) != len(self.early_outputs()) + 1:
+            raise ValueError("WaveGlow.noise_to_latents: %d tensors, expected %d" % (len(noise), len(self.early_outputs()) + 1))
+        return torch.cat(noise[:0:-1] + noise[:1], 1)
+
+    def forward_plan(self, rows, frames):
+        """(rowb, rowr, offsets, P) of the packed row space of the forward direction: utterance b holds ``rows[b]`` real rows
+        in a slot of ``frames[b]`` whole mel frames (hop / n_group rows each, what the upsample product writes); the rows of
+        the last partial frame beyond ``rows[b]`` are marked like halo rows, so they are never computed into h or read back."""
+        H, spf = self.halo(), HOP // self.n_group
+        rowb, rowr, offs = [np.full(H, -1, np.int32)], [np.zeros(H, np.int32)], []
+        pos = H
+        for b, (R, nf) in enumerate(zip(rows, frames)):
+            pad = spf * int(nf) - int(R) + H
+            offs.append(pos)
+            rowb += [np.full(R, b, np.int32), np.full(pad, -1, np.int32)]
+            rowr += [np.arange(R, dtype=np.int32), np.zeros(pad, np.int32)]
+            pos += R + pad
+        return torch.from_numpy(np.concatenate(rowb)), torch.from_numpy(np.concatenate(rowr)), offs, pos
+
+    def _forward(self, spect, audio, lengths, who):
+        """-> (z (B, n_group, T') f32, log_s of all flows (B, sum_k n_half_k, T') f32, rows per utterance (host list))."""
+        dev = self.upsample.weight.device
+        if dev.type != 'cuda' and not nv.validate_only():
+            raise nv.NativeError("WaveGlow: move the module to the MI355X first (.cuda()); there is no CPU path")
+        if not torch.is_tensor(spect) or spect.dim() != 3 or spect.shape[1] != self.n_mel_channels:
+            raise ValueError("WaveGlow.%s: expected (B, %d, N) mels, got %s"
+                             % (who, self.n_mel_channels, tuple(spect.shape) if torch.is_tensor(spect) else type(spect)))
+        if not torch.is_tensor(audio) or audio.dim() != 2 or audio.shape[0] != spect.shape[0]:
+            raise ValueError("WaveGlow.%s: expected (B, T) audio for %d mels, got %s"
+                             % (who, spect.shape[0], tuple(audio.shape) if torch.is_tensor(audio) else type(audio)))
+        for name, t in (("mels", spect), ("audio", audio)):
+            if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+                raise ValueError("WaveGlow.%s: %s must be float32, float16 or bfloat16, got %s" % (who, name, t.dtype))
+        B, nm, N = spect.shape
+        T = audio.shape[1]
+        C, L, G, H = self.n_channels, self.n_layers, self.n_group, self.halo()
+        lens = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if len(lens) != B or min(lens) < 1 or max(lens) > T:
+            raise ValueError("WaveGlow.%s: lengths %s do not fit %d utterances of %d samples" % (who, lens, B, T))
+        if any(t % G for t in lens):
+            raise ValueError("WaveGlow.%s: the sample counts %s must be multiples of n_group = %d (trim the audio; glow.py "
+                             "drops the remainder silently)" % (who, sorted({t for t in lens if t % G}), G))
+        if max(lens) > HOP * N:
+            raise ValueError("WaveGlow.%s: %d samples need more than the %d mel frames given: T must be at most 256 * N = %d"
+                             % (who, max(lens), N, HOP * N))
+        Rm = T // G
+        rows = [t // G for t in lens]
+        frames = [-(-t // HOP) for t in lens]             # mel frames at or past ceil(T_b / 256) cannot reach the audio
+        prec = PRECISIONS[self.precision]
+        pk = self._packed(dev)
+        rowb, rowr, offs, P = self.forward_plan(rows, frames)
+        rowb, rowr = rowb.to(dev), rowr.to(dev)
+        mel = spect.to(device=dev, dtype=torch.float32).contiguous()
+        wav = audio.to(device=dev, dtype=torch.float32).contiguous()
+
+        cond_g, cnd, h, acts, skip, a_rows, mel_cl = self._workspace(P, B, N, dev)
+        n_halves = [c // 2 for c in self.flow_channels]
+        z = torch.zeros(B, G, Rm, dtype=torch.float32, device=dev)
+        log_s = torch.zeros(B, sum(n_halves), Rm, dtype=torch.float32, device=dev)
+
+        # upsample + grouping, trimmed at the front: whole frames into the utterance's own slot of the packed space
+        nv.transpose(mel_cl[:N], mel[0], batch=B, sstride=nm * N, dstride=N * nm)
+        spf = HOP // G
+        for b, nf in enumerate(frames):
+            dst = cond_g[offs[b]:offs[b] + spf * nf].view(nf, HOP * nm)
+            nv.gemm(dst, mel_cl[b * N:b * N + nf], pk['up_w'], bias=pk['up_b'], convA=(nf, nm, 0, -1), fast=prec)
+
+        inner = slice(H, P - H)
+        cond_r, cnd_r, h_r, acts_r, skip_r, rowb_r = cond_g[inner], cnd[inner], h[inner], acts[inner], skip[inner], rowb[inner]
+        fl = pk['flows']
+        nv.wg_head(rowb, rowr, a_rows, G, B, Rm, wave=wav, mix_w=fl[0]['mix_w'], start_w=fl[0]['start_w'],
+                   start_b=fl[0]['start_b'], h=h)
+        z_off = c_off = 0
+        for k in range(self.n_flows):
+            f = fl[k]
+            nv.gemm(cnd_r, cond_r, f['cond_w'], bias=f['cond_b'], fast=prec)
+            for i in range(L):
+                nv.wg_gated(h_r, f['in_w'][i], f['in_b'][i], 2 ** i, cnd_r[:, 2 * C * i:2 * C * (i + 1)], acts_r, prec)
+                last_layer = i == L - 1
+                nv.wg_res_skip(acts_r, f['rs_w'][i], f['rs_b'][i], None if last_layer else h_r, skip_r, i == 0, rowb_r, prec)
+            last = k == self.n_flows - 1
+            n_in = self.flow_channels[k]
+            n_emit = n_in if last else n_in - self.flow_channels[k + 1]
+            nxt = None if last else fl[k + 1]
+            nv.wg_head(rowb, rowr, a_rows, G, B, Rm, skip=skip, end_w=f['end_w'], end_b=f['end_b'],
+                       log_s=log_s[:, c_off:c_off + n_halves[k]], z=z if n_emit else None, z_off=z_off, n_emit=n_emit,
+                       mix_w=nxt['mix_w'] if nxt else None, start_w=nxt['start_w'] if nxt else None,
+                       start_b=nxt['start_b'] if nxt else None, h=h if nxt else None)
+            z_off += n_emit
+            c_off += n_halves[k]
+        return z, log_s, rows
+
+    def _split_log_s(self, log_s):
+        out, c = [], 0
+        for n in self.flow_channels:
+            out.append(log_s[:, c:c + n // 2])
+            c += n // 2
+        return out
+
+    @torch.no_grad()
+    def forward(self, forward_input, lengths=None):
+        """glow.py's ``forward``: ``forward_input = (spect, audio)`` with (B, n_mel, N) mels and (B, T) audio, T a multiple of
+        n_group and at most 256 N (mel frames at or past ceil(T / 256) are not read) -> ``(z, log_s_list, log_det_W_list)``:
+        z (B, n_group, T') with T' = T / n_group, the early outputs first; log_s_list[k] (B, n_half_k, T') (views of one
+        buffer); log_det_W_list[k] = B T' logdet(W_k), a float32 scalar (nan when det W_k < 0).
+        ``lengths``: samples per utterance (ragged: each utterance computed as if alone, z and log_s zero beyond T'_b,
+        log_det_W_list[k] = sum_b T'_b logdet(W_k)).
+        There is no backward pass: the outputs do not require grad, whatever the inputs and the parameters do.
+        After ``.half()``: bf16 compute, z and log_s float16 (log_det_W_list stays float32: it grows with B T')."""
+        spect, audio = forward_input
+        z, log_s, rows = self._forward(spect, audio, lengths, "forward")
+        logdet = self._packed(z.device)['logdet']
+        ld = torch.tensor([sum(rows) * v for v in logdet], dtype=torch.float32, device=z.device)
+        if self.half_io:
+            z, log_s = z.half(), log_s.half()
+        return z, self._split_log_s(log_s), list(ld.unbind(0))
+
+    @torch.no_grad()
+    def nll(self, spect, audio, sigma=1.0, lengths=None):
+        """(B,) float32: the value ``WaveGlowLoss(sigma)`` gives for each utterance alone (nats per sample), from one
+        ``forward`` of the (ragged) batch and the reduction kernel."""
+        z, log_s, rows = self._forward(spect, audio, lengths, "nll")
+        dev = z.device
+        sums = _nll_sums(z, log_s, torch.tensor(rows, dtype=torch.int32, device=dev))
+        logdet = self._packed(dev)['logdet']
+        # each term rounded to float32 as forward() hands it to the loss, summed in float64
+        ld = [float(np.sum(np.float32([r * v for v in logdet]).astype(np.float64))) for r in rows]
+        ld = torch.tensor(ld, dtype=torch.float64, device=dev)
+        numel = torch.tensor([self.n_group * r for r in rows], dtype=torch.float64, device=dev)
+        return ((sums[:, 0] / (2.0 * sigma * sigma) - sums[:, 1] - ld) / numel).float()
+
+
+def _nll_sums(z, log_s, rows):
+    """(B, 2) float64 {sum z^2, sum log_s} per utterance over its first rows[b] rows (t2amd_wg_nll_f32)."""
+    B, _, R = z.shape
+    nchunk = -(-R // nv.wg_nll_chunk())
+    buf = torch.empty(B * nchunk * 2 + B * 2, dtype=torch.float64, device=z.device)
+    out = buf[B * nchunk * 2:].view(B, 2)
+    nv.wg_nll(z, log_s, rows, buf[:B * nchunk * 2], out)
+    return out
+
+
+def _one_buffer(tensors):
+    """The (B, sum c_k, R) tensor whose consecutive channel slices `tensors` are (what ``WaveGlow.forward`` returns), or
+    None."""
+    t0 = tensors[0]
+    if any(t.dtype != torch.float32 or t.dim() != 3 or t.stride() != t0.stride() or t.shape[0] != t0.shape[0]
+           or t.shape[2] != t0.shape[2] or t.device != t0.device for t in tensors):
+        return None
+    if t0.stride(2) != 1 and t0.shape[2] > 1:
+        return None
+    ptr_ = t0.data_ptr()
+    for t in tensors:
+        if t.data_ptr() != ptr_:
+            return None
+        ptr_ += t.shape[1] * t.stride(1) * 4
+    n = sum(t.shape[1] for t in tensors)
+    if t0.stride(0) < n * t0.stride(1):
+        return None
+    return torch.as_strided(t0, (t0.shape[0], n, t0.shape[2]), t0.stride(), t0.storage_offset())
+
+
+class WaveGlowLoss(nn.Module):
+    """glow.py's WaveGlowLoss: ``(sum(z^2) / (2 sigma^2) - sum_k sum(log_s_k) - sum_k log_det_W_k) / z.numel()`` of the
+    output of ``WaveGlow.forward``, a float32 scalar.  The two sums run on the reduction kernel (fixed order, float64
+    accumulation).  No backward pass: the result does not require grad."""
+
+    def __init__(self, sigma=1.0):
+        super().__init__()
+        self.sigma = sigma
+
+    @torch.no_grad()
+    def forward(self, model_output):
+        z, log_s_list, log_det_W_list = model_output
+        if z.dim() != 3:
+            raise ValueError("WaveGlowLoss: expected (B, n_group, T') latents, got %s" % (tuple(z.shape),))
+        if not z.is_cuda and not nv.validate_only():
+            raise nv.NativeError("WaveGlowLoss: the latents must be on the MI355X; there is no CPU path")
+        log_s_list = list(log_s_list)
+        for t in log_s_list:
+            if t.dim() != 3 or t.shape[0] != z.shape[0] or t.shape[2] != z.shape[2]:
+                raise ValueError("WaveGlowLoss: log_s %s beside latents %s" % (tuple(t.shape), tuple(z.shape)))
+        z32 = z.float()
+        if z32.stride(2) != 1:
+            z32 = z32.contiguous()
+        log_s = None
+        if log_s_list:
+            log_s = _one_buffer(log_s_list)
+            if log_s is None:
+                log_s = torch.cat([t.float() for t in log_s_list], 1)
+        rows = torch.full((z.shape[0],), z.shape[2], dtype=torch.int32, device=z.device)
+        sums = _nll_sums(z32, log_s, rows).sum(0)
+        ld = torch.stack([torch.as_tensor(t, dtype=torch.float32, device=z.device) for t in log_det_W_list]).double().sum()
+        sigma = self.sigma
+        return ((sums[0] / (2.0 * sigma * sigma) - sums[1] - ld) / z.numel()).float()
 
 
 class Denoiser(nn.Module):
