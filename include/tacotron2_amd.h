@@ -1006,6 +1006,50 @@ int t2amd_wg_nll_f32(const float* z, long long zb, long long zc, int nz, const f
                      const int* len, int B, long long R, double* partial, long long nchunk, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * WaveGlow backward pass (csrc/waveglow_bwd.hip and the training entries of csrc/waveglow_fwd.hip / waveglow_layer.hip;
+ * WaveGlow.training_loss).  loss = (sum z^2 / (2 sigma^2) - sum log_s - sum log det W) / numel; c1 = 1 / (sigma^2 numel),
+ * c2 = -1 / numel.  No atomics anywhere: two runs give identical bits.
+ * ------------------------------------------------------------------------------------ */
+/* t2amd_wg_layer_f32 with the training forward's extra outputs and the data-gradient mode:
+ * mode 0, gate != NULL: gate[m][0:C] = the tanh values, gate[m][C:2C] = the sigmoid values of acts (channel order);
+ * mode 1, h_out != NULL: h_out[m][n] = h[m][n] + . instead of h[m][n] += . (h itself is left as the layer read it);
+ * mode 2 (N = C, taps 3, Cin = 2C, X = the image of d_pre, W [C][3 * 2C] the transposed in-layer weights with the taps
+ *   mirrored, bias unused): h[m][n] += . (or = . when skip_store) on rows with rowb[m] >= 0. */
+int t2amd_wg_layer_train_f32(const float* X, long long ldx, const float* W, const float* bias, int M, int N, int Cin, int taps,
+                             int dil, int mode, const float* cnd, long long ldcnd, float* acts, long long ldacts, float* h,
+                             long long ldh, int nres, float* skip, long long ldskip, int skip_store, const int* rowb,
+                             float* gate, long long ldgate, float* h_out, long long ldhout, int precision, void* stream);
+/* t2amd_wg_head_f32 that also keeps, per real row, sv[p][0:n_cur] = x (after the coupling, before the early output and the
+ * mix) and sv[p][n_group:n_group + n_out] = a (after the mix); sv NULL: t2amd_wg_head_f32 itself.  ldsv >= 2 n_group. */
+int t2amd_wg_head_save_f32(const float* skip, long long ldskip, int C, const float* end_w, const float* end_b, int n_in,
+                           float* log_s, long long lsb, long long lsc, const float* wave, long long ldwave, float* audio,
+                           long long ldaudio, float* z, long long zb, long long zc, int z_off, int n_emit,
+                           const float* mix_w, const float* start_w, const float* start_b, float* h, long long ldh,
+                           const int* rowb, const int* rowr, long long P, int n_group, int B, long long R, float* sv,
+                           long long ldsv, void* stream);
+/* Backward of one flow head call over P packed rows (t2amd_wg_head_bwd_rows() rows per workgroup).  With x_sv / a_sv the
+ * rows that call kept, a_in the a rows of the call before it (the coupling's input), dh0 the gradient of the opened flow's
+ * layer-0 input and dA the gradient of the audio rows (in: of the opened flow's, out: of the closed flow's):
+ *   da = dA[p][0:n_out] + [start_w^T . dh0[p] | 0];  dx[n_emit:] = mix_w^T . da;  dx[k] = c1 x[k] for k < n_emit;
+ *   de = [dx1, dx1 x1 exp(log_s) + c2];  dA[p][0:n_in] = [dx0, dx1 exp(log_s)];  d_skip[p] = end_w^T . de;
+ * and per workgroup the partial sums [d_end_w (n_in C) | d_end_b (n_in) | d_start_w (C n_out/2) | d_start_b (C) | d_mix
+ * (n_out^2)] at partial + workgroup * npart (the parts of a NULL end_w / mix_w are absent; npart is their exact total).
+ * end_w NULL: the first call (the waveform; dx is dropped); mix_w NULL: the last call (n_emit == n_in). */
+int t2amd_wg_head_bwd_rows(void);
+int t2amd_wg_head_bwd_f32(const float* skip, long long ldskip, int C, const float* end_w, int n_in, const float* log_s,
+                          long long lsb, long long lsc, const float* a_in, long long ldain, const float* x_sv, long long ldx,
+                          const float* a_sv, long long ldasv, float* dA, long long lddA, const float* dh0, long long lddh,
+                          const float* mix_w, const float* start_w, int n_emit, float* d_skip, long long ldds, float* partial,
+                          long long npart, const int* rowb, const int* rowr, long long P, int n_group, int B, long long R,
+                          float c1, float c2, void* stream);
+/* out[i] = sum over blk < nblk, in that order, of partial[blk * n + i]. */
+int t2amd_wg_partial_sum_f32(const float* partial, long long nblk, long long n, float* out, void* stream);
+/* Gate backward on rows with rowb[m] >= 0 (others are not written), gate[m] = [t (C) | s (C)] as mode 0 kept them:
+ * d_pre[m][c] = d_acts[m][c] s (1 - t^2);  d_pre[m][C + c] = d_acts[m][c] t s (1 - s);  acts[m][c] = t s. */
+int t2amd_wg_gate_bwd_f32(const float* d_acts, long long ldd, const float* gate, long long ldg, const int* rowb, long long M,
+                          int C, float* d_pre, long long ldp, float* acts, long long lda, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Optimiser step: global-norm clipping + Adam over all parameter
  * tensors in two launches.  Replaces reference train.py:233-236
  *   grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), grad_clip_thresh)

@@ -20,13 +20,14 @@
 //   z[b][z_off + k][r] = x[k] for k < n_emit                 (an early output; everything that is left on the last call)
 //   a = mix_w . x[n_emit:],  audio[p][0:n_out] = a           (mix_w [n_out][n_out], n_out = n_in - n_emit; NULL: the last call)
 //   h[p][c] = start_b[c] + start_w[c] . a[0:n_out/2]         (the next flow's start)
+// sv != NULL (the training forward): sv[p][0:n_cur] = x and sv[p][n_group:n_group + n_out] = a are kept for the backward pass.
 __global__ void __launch_bounds__(256) wg_head_kernel(
     const float* __restrict__ skip, long long ldskip, int C, const float* __restrict__ end_w, const float* __restrict__ end_b,
     int n_in, float* __restrict__ log_s, long long lsb, long long lsc, const float* __restrict__ wave, long long ldwave,
     float* __restrict__ audio, long long ldaudio, float* __restrict__ z, long long zb, long long zc, int z_off, int n_emit,
     const float* __restrict__ mix_w, const float* __restrict__ start_w, const float* __restrict__ start_b,
     float* __restrict__ h, long long ldh, const int* __restrict__ rowb, const int* __restrict__ rowr, long long P, int n_group,
-    int B, long long R) {
+    int B, long long R, float* __restrict__ sv, long long ldsv) {
     __shared__ float s_end[WG_MAXG * WG_MAXC];
     __shared__ float s_start[WG_MAXC * (WG_MAXG / 2)];
     __shared__ float s_mix[WG_MAXG * WG_MAXG];
@@ -84,12 +85,15 @@ __global__ void __launch_bounds__(256) wg_head_kernel(
             for (int g = 0; g < n_group; ++g) x[g] = wave[b * ldwave + r * n_group + g];
         }
         for (int k = 0; k < n_emit; ++k) z[b * zb + (z_off + k) * zc + r] = x[k];
+        if (sv)
+            for (int k = 0; k < n_cur; ++k) sv[p * ldsv + k] = x[k];
         if (mix_w) {
             for (int i = 0; i < n_out; ++i) {
                 float acc = 0.0f;
                 for (int j = 0; j < n_out; ++j) acc += s_mix[i * n_out + j] * x[n_emit + j];
                 s_a[row][i] = acc;
                 audio[p * ldaudio + i] = acc;
+                if (sv) sv[p * ldsv + n_group + i] = acc;
             }
         }
     }
@@ -111,12 +115,13 @@ __global__ void __launch_bounds__(256) wg_head_kernel(
     }
 }
 
-extern "C" int t2amd_wg_head_f32(const float* skip, long long ldskip, int C, const float* end_w, const float* end_b, int n_in,
-                                 float* log_s, long long lsb, long long lsc, const float* wave, long long ldwave,
-                                 float* audio, long long ldaudio, float* z, long long zb, long long zc, int z_off, int n_emit,
-                                 const float* mix_w, const float* start_w, const float* start_b, float* h, long long ldh,
-                                 const int* rowb, const int* rowr, long long P, int n_group, int B, long long R,
-                                 void* stream) {
+extern "C" int t2amd_wg_head_save_f32(const float* skip, long long ldskip, int C, const float* end_w, const float* end_b,
+                                      int n_in, float* log_s, long long lsb, long long lsc, const float* wave, long long ldwave,
+                                      float* audio, long long ldaudio, float* z, long long zb, long long zc, int z_off,
+                                      int n_emit, const float* mix_w, const float* start_w, const float* start_b, float* h,
+                                      long long ldh, const int* rowb, const int* rowr, long long P, int n_group, int B,
+                                      long long R, float* sv, long long ldsv, void* stream) {
+    T2_REQUIRE(!sv || ldsv >= 2 * n_group, "wg_head: saved rows hold 2 n_group values");
     T2_REQUIRE(rowb && rowr && audio, "wg_head: null operand");
     T2_REQUIRE(P > 0 && B > 0 && R > 0, "wg_head: no rows");
     T2_REQUIRE(C > 0 && C <= WG_MAXC, "wg_head: C must be in 1..512");
@@ -150,9 +155,19 @@ extern "C" int t2amd_wg_head_f32(const float* skip, long long ldskip, int C, con
     T2_REQUIRE(nblk <= 0x7fffffffLL, "wg_head: too many rows");
     T2_LAUNCH(wg_head_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, skip, ldskip, C, end_w, end_b, n_in,
               log_s, lsb, lsc, wave, ldwave, audio, ldaudio, z, zb, zc, z_off, n_emit, mix_w, start_w, start_b, h, ldh, rowb,
-              rowr, P, n_group, B, R);
+              rowr, P, n_group, B, R, sv, ldsv);
     T2_LAUNCH_CHECK();
     return T2AMD_OK;
+}
+
+extern "C" int t2amd_wg_head_f32(const float* skip, long long ldskip, int C, const float* end_w, const float* end_b, int n_in,
+                                 float* log_s, long long lsb, long long lsc, const float* wave, long long ldwave,
+                                 float* audio, long long ldaudio, float* z, long long zb, long long zc, int z_off, int n_emit,
+                                 const float* mix_w, const float* start_w, const float* start_b, float* h, long long ldh,
+                                 const int* rowb, const int* rowr, long long P, int n_group, int B, long long R,
+                                 void* stream) {
+    return t2amd_wg_head_save_f32(skip, ldskip, C, end_w, end_b, n_in, log_s, lsb, lsc, wave, ldwave, audio, ldaudio, z, zb, zc,
+                                  z_off, n_emit, mix_w, start_w, start_b, h, ldh, rowb, rowr, P, n_group, B, R, nullptr, 0, stream);
 }
 
 // The two sums of the negative log-likelihood per utterance, in a fixed order (two stages, no atomics): the numbers of an

@@ -13,6 +13,11 @@
 // mode 1 (residual / skip product, K = C): column n < nres is added into h (rows whose rowb >= 0 only, so halo rows stay
 // zero); column n >= nres goes to skip[m][n - nres] (stored when skip_store, else added).
 //
+// mode 2 (the in-layer product's data gradient, N = C, K = 3 * 2C over the image of d_pre, W = the transposed weights with
+// the taps mirrored): column n is added into h[m][n] (stored when skip_store) on rows whose rowb >= 0; no bias.
+// The training forward passes two more outputs, NULL otherwise: mode 0 keeps the two gate values in gate[m][0:2C], mode 1
+// writes the updated residual rows to h_out (the next layer's own image) and leaves h as the backward pass needs it.
+//
 // Precision 0 is the exact-f32 MFMA (v_mfma_f32_32x32x2_f32), 1 split-bf16 x 3 and 2 plain bf16 on
 // v_mfma_f32_32x32x16_bf16, with the operand splitting of gemm.hip's bf16 kernels.
 #include "common.h"
@@ -33,6 +38,10 @@ struct WgLayerParams {
     float* skip;
     long long ldskip;
     const int* rowb;
+    float* gate;          // mode 0, optional: gate[m] = [tanh (C) | sigmoid (C)] kept for the backward pass
+    long long ldgate;
+    float* h_out;         // mode 1, optional: the updated residual rows go here instead of into h
+    long long ldhout;
 };
 
 __device__ __forceinline__ float wg_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -56,7 +65,31 @@ __device__ __forceinline__ void wg_layer_epilogue(const WgLayerParams& p, f32x16
                     const float* cr = p.cnd + (long long)gm * p.ldcnd;
                     const float t = acc[tm][0][r] + bt + cr[c];
                     const float s = acc[tm][1][r] + bs + cr[C + c];
-                    p.acts[(long long)gm * p.ldacts + c] = tanhf(t) * wg_sigmoid(s);
+                    const float tt = tanhf(t), ss = wg_sigmoid(s);
+                    p.acts[(long long)gm * p.ldacts + c] = tt * ss;
+                    if (p.gate) {
+                        p.gate[(long long)gm * p.ldgate + c] = tt;
+                        p.gate[(long long)gm * p.ldgate + C + c] = ss;
+                    }
+                }
+            }
+        }
+        return;
+    }
+    if (p.mode == 2) {
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) {
+            const int gn = cbase + tn * 32 + l31;
+            if (gn >= p.N) continue;
+#pragma unroll
+            for (int tm = 0; tm < 2; ++tm) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int gm = row0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                    if (gm < p.M && p.rowb[gm] >= 0) {
+                        float* hp = p.h + (long long)gm * p.ldh + gn;
+                        *hp = p.skip_store ? acc[tm][tn][r] : *hp + acc[tm][tn][r];
+                    }
                 }
             }
         }
@@ -76,8 +109,9 @@ __device__ __forceinline__ void wg_layer_epilogue(const WgLayerParams& p, f32x16
                     const float v = acc[tm][tn][r] + b;
                     if (gn < p.nres) {
                         if (p.rowb[gm] >= 0) {
-                            float* hp = p.h + (long long)gm * p.ldh + gn;
-                            *hp = *hp + v;
+                            const float* hp = p.h + (long long)gm * p.ldh + gn;
+                            float* ho = p.h_out ? p.h_out + (long long)gm * p.ldhout + gn : p.h + (long long)gm * p.ldh + gn;
+                            *ho = *hp + v;
                         }
                     } else {
                         float* sp = p.skip + (long long)gm * p.ldskip + (gn - p.nres);
@@ -279,11 +313,12 @@ __global__ __launch_bounds__(256) void wg_layer_bf16_kernel(WgLayerParams p) {
     wg_layer_epilogue(p, acc, row0, col0, wm, wn, lane);
 }
 
-extern "C" int t2amd_wg_layer_f32(const float* X, long long ldx, const float* W, const float* bias, int M, int N, int Cin,
-                                  int taps, int dil, int mode, const float* cnd, long long ldcnd, float* acts,
-                                  long long ldacts, float* h, long long ldh, int nres, float* skip, long long ldskip,
-                                  int skip_store, const int* rowb, int precision, void* stream) {
-    T2_REQUIRE(X && W && bias, "wg_layer: null operand");
+extern "C" int t2amd_wg_layer_train_f32(const float* X, long long ldx, const float* W, const float* bias, int M, int N, int Cin,
+                                        int taps, int dil, int mode, const float* cnd, long long ldcnd, float* acts,
+                                        long long ldacts, float* h, long long ldh, int nres, float* skip, long long ldskip,
+                                        int skip_store, const int* rowb, float* gate, long long ldgate, float* h_out,
+                                        long long ldhout, int precision, void* stream) {
+    T2_REQUIRE(X && W && (bias || mode == 2), "wg_layer: null operand");
     T2_REQUIRE(M > 0 && N > 0 && Cin > 0 && taps >= 1 && taps % 2 == 1 && dil >= 1, "wg_layer: bad dims");
     T2_REQUIRE(Cin % 32 == 0, "wg_layer: input channels must be a multiple of 32");
     T2_REQUIRE(ldx >= Cin && ldx % 4 == 0 && t2_aligned16(X) && t2_aligned16(W), "wg_layer: X / W must be 16-byte aligned rows");
@@ -293,6 +328,9 @@ extern "C" int t2amd_wg_layer_f32(const float* X, long long ldx, const float* W,
     p.M = M; p.N = N; p.K = taps * Cin; p.Cin = Cin; p.taps = taps; p.dil = dil; p.mode = mode;
     p.cnd = cnd; p.ldcnd = ldcnd; p.acts = acts; p.ldacts = ldacts;
     p.h = h; p.ldh = ldh; p.nres = nres; p.skip_store = skip_store; p.skip = skip; p.ldskip = ldskip; p.rowb = rowb;
+    p.gate = gate; p.ldgate = ldgate; p.h_out = h_out; p.ldhout = ldhout;
+    T2_REQUIRE(!gate || (mode == 0 && ldgate >= N), "wg_layer: gate values are kept by the gated product, 2C per row");
+    T2_REQUIRE(!h_out || (mode == 1 && nres > 0 && ldhout >= nres), "wg_layer: h_out belongs to the residual columns");
     if (mode == 0) {
         T2_REQUIRE(cnd && acts, "wg_layer: gated product needs cnd and acts");
         T2_REQUIRE(N % 128 == 0, "wg_layer: gated product needs N = 2C with C a multiple of 64");
@@ -303,8 +341,10 @@ extern "C" int t2amd_wg_layer_f32(const float* X, long long ldx, const float* W,
         T2_REQUIRE(nres >= 0 && nres < N, "wg_layer: nres out of range");
         T2_REQUIRE(nres == 0 || (h && ldh >= nres), "wg_layer: residual columns need h");
         T2_REQUIRE(ldskip >= N - nres, "wg_layer: skip rows too short");
+    } else if (mode == 2) {
+        T2_REQUIRE(h && rowb && ldh >= N, "wg_layer: the data gradient needs h and rowb");
     } else {
-        T2_FAIL("wg_layer: mode must be 0 (gated) or 1 (residual / skip)");
+        T2_FAIL("wg_layer: mode must be 0 (gated), 1 (residual / skip) or 2 (data gradient)");
     }
     dim3 grid(t2_cdiv(N, 128), t2_cdiv(M, 128));
     T2_REQUIRE(grid.y <= 65535, "wg_layer: too many rows");
@@ -317,4 +357,13 @@ extern "C" int t2amd_wg_layer_f32(const float* X, long long ldx, const float* W,
         T2_LAUNCH(wg_layer_bf16_kernel<false>, grid, dim3(256), 0, s, p);
     T2_LAUNCH_CHECK();
     return T2AMD_OK;
+}
+
+extern "C" int t2amd_wg_layer_f32(const float* X, long long ldx, const float* W, const float* bias, int M, int N, int Cin,
+                                  int taps, int dil, int mode, const float* cnd, long long ldcnd, float* acts,
+                                  long long ldacts, float* h, long long ldh, int nres, float* skip, long long ldskip,
+                                  int skip_store, const int* rowb, int precision, void* stream) {
+    T2_REQUIRE(mode == 0 || mode == 1, "wg_layer: mode must be 0 (gated) or 1 (residual / skip)");
+    return t2amd_wg_layer_train_f32(X, ldx, W, bias, M, N, Cin, taps, dil, mode, cnd, ldcnd, acts, ldacts, h, ldh, nres, skip,
+                                    ldskip, skip_store, rowb, nullptr, 0, nullptr, 0, precision, stream);
 }

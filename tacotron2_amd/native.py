@@ -288,6 +288,8 @@ SYMBOLS = [
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
+    "t2amd_wg_layer_train_f32", "t2amd_wg_head_save_f32", "t2amd_wg_head_bwd_rows", "t2amd_wg_head_bwd_f32",
+    "t2amd_wg_partial_sum_f32", "t2amd_wg_gate_bwd_f32",
     "t2amd_optim_chunk", "t2amd_grad_norm_f32", "t2amd_adam_step_f32",
     "t2amd_decoder_persist_mailbox_bytes", "t2amd_decoder_persist_supported", "t2amd_decoder_infer_persistent_f32",
     "t2amd_loss_workspace_doubles", "t2amd_tacotron2_loss_fwd_f32", "t2amd_tacotron2_loss_bwd_f32",
@@ -395,6 +397,15 @@ def _argtypes():
                               _P, _L, _I, _I, _L, _P],
         "t2amd_wg_nll_chunk": [],
         "t2amd_wg_nll_f32": [_P, _L, _L, _I, _P, _L, _L, _I, _P, _I, _L, _P, _L, _P, _P],
+        "t2amd_wg_layer_train_f32": [_P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _I, _P, _L, _I, _P, _P, _L,
+                                     _P, _L, _I, _P],
+        "t2amd_wg_head_save_f32": [_P, _L, _I, _P, _P, _I, _P, _L, _L, _P, _L, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _L,
+                                   _P, _P, _L, _I, _I, _L, _P, _L, _P],
+        "t2amd_wg_head_bwd_rows": [],
+        "t2amd_wg_head_bwd_f32": [_P, _L, _I, _P, _I, _P, _L, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _I, _P, _L,
+                                  _P, _L, _P, _P, _L, _I, _I, _L, _F, _F, _P],
+        "t2amd_wg_partial_sum_f32": [_P, _L, _L, _P, _P],
+        "t2amd_wg_gate_bwd_f32": [_P, _L, _P, _L, _P, _L, _I, _P, _L, _P, _L, _P],
         "t2amd_optim_chunk": [],
         "t2amd_grad_norm_f32": [pt(TensorList), _F, _P, _P, _P],
         "t2amd_adam_step_f32": [pt(TensorList), pt(AdamHyper), _P, _P],
@@ -1686,9 +1697,10 @@ def _opt(t, dtype=torch.float32):
     return ptr(_fullc(t), dtype) if t is not None else None
 
 
-def wg_gated(X, W, bias, dil, cnd, acts, precision):
+def wg_gated(X, W, bias, dil, cnd, acts, precision, gate=None):
     """acts[m][0:C] = tanh * sigmoid of the dilated kernel-3 product of the halo image X (a view whose rows continue
-    for at least `dil` rows on both sides) with the gate-packed weights W [2C][3C] (+ bias, + cnd[m][0:2C])."""
+    for at least `dil` rows on both sides) with the gate-packed weights W [2C][3C] (+ bias, + cnd[m][0:2C]).
+    gate [M][2C] (the training forward): the tanh values and the sigmoid values, in channel order, kept for the backward pass."""
     px, ldx, M, Cin = _mat(X)
     pw, _, N, K = _mat(W)
     pc, ldc, Mc, Nc = _mat(cnd)
@@ -1696,14 +1708,22 @@ def wg_gated(X, W, bias, dil, cnd, acts, precision):
     if K != 3 * Cin or Mc != M or Ma != M or Nc != N or 2 * Ca != N or bias.numel() != N:
         raise NativeError("wg_gated: shape mismatch X=%s W=%s cnd=%s acts=%s" % (tuple(X.shape), tuple(W.shape),
                                                                                 tuple(cnd.shape), tuple(acts.shape)))
+    if gate is not None:
+        pg, ldg, Mg, Ng = _mat(gate)
+        if Mg != M or Ng != N:
+            raise NativeError("wg_gated: gate %s for %d rows of %d values" % (tuple(gate.shape), M, N))
+        _check(load().t2amd_wg_layer_train_f32(px, _i64(ldx), pw, ptr(_fullc(bias)), M, N, Cin, 3, int(dil), 0, pc, _i64(ldc),
+                                               pa, _i64(lda), None, 0, 0, None, 0, 0, None, pg, _i64(ldg), None, 0,
+                                               int(precision), _stream()), "t2amd_wg_layer_train_f32")
+        return
     _check(load().t2amd_wg_layer_f32(px, _i64(ldx), pw, ptr(_fullc(bias)), M, N, Cin, 3, int(dil), 0, pc, _i64(ldc), pa,
                                      _i64(lda), None, 0, 0, None, 0, 0, None, int(precision), _stream()),
            "t2amd_wg_layer_f32")
 
 
-def wg_res_skip(acts, W, bias, h, skip, skip_store, rowb, precision):
+def wg_res_skip(acts, W, bias, h, skip, skip_store, rowb, precision, h_out=None):
     """h[m] += (acts . W^T + bias)[0:C] on rows with rowb >= 0 (h None: the last layer, no residual half);
-    skip[m] (+)= the remaining columns."""
+    skip[m] (+)= the remaining columns.  h_out (the training forward): h_out[m] = h[m] + ... instead, h is left as it is."""
     px, ldx, M, Cin = _mat(acts)
     pw, _, N, K = _mat(W)
     ps, lds, Ms, Cs = _mat(skip)
@@ -1716,9 +1736,36 @@ def wg_res_skip(acts, W, bias, h, skip, skip_store, rowb, precision):
     if K != Cin or Ms != M or N - nres != Cs or bias.numel() != N or rowb.numel() < M:
         raise NativeError("wg_res_skip: shape mismatch acts=%s W=%s skip=%s" % (tuple(acts.shape), tuple(W.shape),
                                                                                tuple(skip.shape)))
+    if h_out is not None:
+        if h is None:
+            raise NativeError("wg_res_skip: h_out without h")
+        po, ldo, Mo, No = _mat(h_out)
+        if Mo != M or No != nres:
+            raise NativeError("wg_res_skip: h_out %s beside h %s" % (tuple(h_out.shape), tuple(h.shape)))
+        _check(load().t2amd_wg_layer_train_f32(px, _i64(ldx), pw, ptr(_fullc(bias)), M, N, Cin, 1, 1, 1, None, 0, None, 0, ph,
+                                               _i64(ldh), nres, ps, _i64(lds), 1 if skip_store else 0,
+                                               ptr(rowb, torch.int32), None, 0, po, _i64(ldo), int(precision), _stream()),
+               "t2amd_wg_layer_train_f32")
+        return
     _check(load().t2amd_wg_layer_f32(px, _i64(ldx), pw, ptr(_fullc(bias)), M, N, Cin, 1, 1, 1, None, 0, None, 0, ph,
                                      _i64(ldh), nres, ps, _i64(lds), 1 if skip_store else 0, ptr(rowb, torch.int32),
                                      int(precision), _stream()), "t2amd_wg_layer_f32")
+
+
+def wg_dgrad(d_pre, Wt, dil, dh, store, rowb, precision):
+    """The in-layer product's data gradient in one launch: dh[m] (+)= sum over the three taps of d_pre[m -+ dil] . W on rows
+    with rowb >= 0 (``store``: plain store).  d_pre [M][2C] is a view whose rows continue, zero, for at least `dil` rows on
+    both sides; Wt [C][3 * 2C] holds the transposed weights with the taps mirrored (WaveGlow._packed's ``in_wT``)."""
+    px, ldx, M, Cin = _mat(d_pre)
+    pw, _, N, K = _mat(Wt)
+    ph, ldh, Mh, Nh = _mat(dh)
+    if K != 3 * Cin or Mh != M or Nh != N or rowb.numel() < M:
+        raise NativeError("wg_dgrad: shape mismatch d_pre=%s Wt=%s dh=%s" % (tuple(d_pre.shape), tuple(Wt.shape),
+                                                                            tuple(dh.shape)))
+    _fullc(Wt)
+    _check(load().t2amd_wg_layer_train_f32(px, _i64(ldx), pw, None, M, N, Cin, 3, int(dil), 2, None, 0, None, 0, ph, _i64(ldh),
+                                           0, None, 0, 1 if store else 0, ptr(rowb, torch.int32), None, 0, None, 0,
+                                           int(precision), _stream()), "t2amd_wg_layer_train_f32")
 
 
 def wg_tail(rowb, rowr, audio, n_group, skip=None, end_w=None, end_b=None, winv=None, z=None, sigma=0.0,
@@ -1773,8 +1820,9 @@ def _chan_rows(t, what, dtype=torch.float32):
 
 
 def wg_head(rowb, rowr, audio, n_group, B, R, skip=None, end_w=None, end_b=None, log_s=None, wave=None, z=None, z_off=0,
-            n_emit=0, mix_w=None, start_w=None, start_b=None, h=None):
-    """The flow head over every packed row (see the header).  log_s (B, n_in / 2, R) and z (B, n_group, R) with contiguous
+            n_emit=0, mix_w=None, start_w=None, start_b=None, h=None, save=None):
+    """The flow head over every packed row (see the header).  save [P][2 n_group] (the training forward) keeps the rows
+    before and after the mix.  log_s (B, n_in / 2, R) and z (B, n_group, R) with contiguous
     rows (any batch / channel stride); wave (B, >= n_group R) waveform rows; end_w (n_in, C), mix_w (n_out, n_out) and
     start_w (C, n_out / 2) contiguous."""
     P = rowb.numel()
@@ -1810,6 +1858,16 @@ def wg_head(rowb, rowr, audio, n_group, B, R, skip=None, end_w=None, end_b=None,
     if mix_w is not None and (mix_w.dim() != 2 or mix_w.shape[0] != mix_w.shape[1] or start_w is None
                               or start_w.dim() != 2 or 2 * start_w.shape[1] != mix_w.shape[0]):
         raise NativeError("wg_head: mix_w (n, n) needs start_w (C, n / 2)")
+    if save is not None:
+        psv, ldsv, Psv, nsv = _mat(save)
+        if Psv != P or nsv != 2 * n_group:
+            raise NativeError("wg_head: save %s for %d packed rows of 2 x %d values" % (tuple(save.shape), P, n_group))
+        _check(load().t2amd_wg_head_save_f32(ps, _i64(lds), int(nc), _opt(end_w), _opt(end_b), int(n_in), pl, _i64(lsb),
+                                             _i64(lsc), pw, _i64(ldw), pa, _i64(lda), pz, _i64(zb), _i64(zc), int(z_off),
+                                             int(n_emit), _opt(mix_w), _opt(start_w), _opt(start_b), ph, _i64(ldh),
+                                             ptr(rowb, torch.int32), ptr(rowr, torch.int32), _i64(P), int(n_group), int(B),
+                                             _i64(R), psv, _i64(ldsv), _stream()), "t2amd_wg_head_save_f32")
+        return
     _check(load().t2amd_wg_head_f32(ps, _i64(lds), int(nc), _opt(end_w), _opt(end_b), int(n_in), pl, _i64(lsb), _i64(lsc),
                                     pw, _i64(ldw), pa, _i64(lda), pz, _i64(zb), _i64(zc), int(z_off), int(n_emit),
                                     _opt(mix_w), _opt(start_w), _opt(start_b), ph, _i64(ldh), ptr(rowb, torch.int32),
@@ -1838,6 +1896,89 @@ def wg_nll(z, log_s, rows, partial, out):
     _check(load().t2amd_wg_nll_f32(pz, _i64(zb), _i64(zc), int(nz), pl, _i64(lb), _i64(lc), int(nls), ptr(rows, torch.int32),
                                    int(B), _i64(R), ptr(_fullc(partial), torch.float64), _i64(nchunk),
                                    ptr(_fullc(out), torch.float64), _stream()), "t2amd_wg_nll_f32")
+
+
+# ----------------------------------------------------------------------------
+# WaveGlow backward pass (csrc/waveglow_bwd.hip)
+# ----------------------------------------------------------------------------
+def wg_head_bwd_rows():
+    return int(load().t2amd_wg_head_bwd_rows())
+
+
+def wg_head_bwd_sizes(C, n_in, n_out):
+    """Number of small gradients one head call produces: [end_w | end_b] (n_in > 0) + [start_w | start_b | mix] (n_out > 0)."""
+    n = n_in * C + n_in if n_in else 0
+    return n + (C * (n_out // 2) + C + n_out * n_out if n_out else 0)
+
+
+def wg_head_bwd(rowb, rowr, n_group, B, R, c1, c2, x_sv, partial, n_emit=0, skip=None, end_w=None, log_s=None, a_in=None,
+                dA=None, d_skip=None, dh0=None, mix_w=None, start_w=None, a_sv=None):
+    """Backward of one flow head call (see the header) -> (workgroups, small gradients per workgroup): ``partial`` holds the
+    per-workgroup partial sums for ``wg_partial_sum``.  x_sv / a_sv: the rows the call kept; a_in: the a rows of the call
+    before; dA [P][>= n_group] in / out; dh0 [P][C]; d_skip [P][C] out."""
+    P = rowb.numel()
+    if rowr.numel() != P:
+        raise NativeError("wg_head_bwd: %d rowr for %d packed rows" % (rowr.numel(), P))
+
+    def rows(t, what):
+        if t is None:
+            return None, 0, 0
+        p_, ld, Pt, n = _mat(t)
+        if Pt != P:
+            raise NativeError("wg_head_bwd: %s has %d rows for %d packed rows" % (what, Pt, P))
+        return p_, ld, n
+
+    n_in, C = (end_w.shape[0], end_w.shape[1]) if end_w is not None else (0, 0)
+    if start_w is not None:
+        C = C or start_w.shape[0]
+    n_cur = n_in if end_w is not None else n_group
+    n_out = n_cur - n_emit if mix_w is not None else 0
+    if mix_w is not None and (mix_w.dim() != 2 or tuple(mix_w.shape) != (n_out, n_out) or start_w is None
+                              or start_w.dim() != 2 or tuple(start_w.shape) != (C, n_out // 2)):
+        raise NativeError("wg_head_bwd: mix_w (n_out, n_out) needs start_w (C, n_out / 2), n_out = %d" % n_out)
+    ps, lds, _ = rows(skip, "skip")
+    pai, ldai, _ = rows(a_in, "a_in")
+    px, ldx, _ = rows(x_sv, "x_sv")
+    pas, ldas, _ = rows(a_sv, "a_sv")
+    pdA, lddA, _ = rows(dA, "dA")
+    pdh, lddh, _ = rows(dh0, "dh0")
+    pds, ldds, _ = rows(d_skip, "d_skip")
+    pl, lsb, lsc = None, 0, 0
+    if log_s is not None:
+        pl, lsb, lsc, nl, Rl = _chan_rows(log_s, "wg_head_bwd: log_s")
+        if (nl, Rl, log_s.shape[0]) != (n_in // 2, R, B):
+            raise NativeError("wg_head_bwd: log_s %s for B=%d, n_in=%d, R=%d" % (tuple(log_s.shape), B, n_in, R))
+    npart = wg_head_bwd_sizes(C, n_in, n_out)
+    nblk = -(-P // wg_head_bwd_rows())
+    if partial.numel() < nblk * npart:
+        raise NativeError("wg_head_bwd: partial holds %d values, %d workgroups x %d needed" % (partial.numel(), nblk, npart))
+    _check(load().t2amd_wg_head_bwd_f32(ps, _i64(lds), int(C), _opt(end_w), int(n_in), pl, _i64(lsb), _i64(lsc), pai, _i64(ldai),
+                                        px, _i64(ldx), pas, _i64(ldas), pdA, _i64(lddA), pdh, _i64(lddh), _opt(mix_w),
+                                        _opt(start_w), int(n_emit), pds, _i64(ldds), ptr(_fullc(partial)), _i64(npart),
+                                        ptr(rowb, torch.int32), ptr(rowr, torch.int32), _i64(P), int(n_group), int(B), _i64(R),
+                                        _F(c1), _F(c2), _stream()), "t2amd_wg_head_bwd_f32")
+    return nblk, npart
+
+
+def wg_partial_sum(partial, nblk, n, out):
+    """out[0:n] = sum over the first nblk blocks of n values of ``partial``, in block order."""
+    if partial.numel() < nblk * n or out.numel() != n:
+        raise NativeError("wg_partial_sum: %d partials, %d outputs for %d blocks of %d" % (partial.numel(), out.numel(), nblk, n))
+    _check(load().t2amd_wg_partial_sum_f32(ptr(_fullc(partial)), _i64(nblk), _i64(n), ptr(_fullc(out)), _stream()),
+           "t2amd_wg_partial_sum_f32")
+
+
+def wg_gate_bwd(d_acts, gate, rowb, d_pre, acts):
+    """d_pre [M][2C] and acts [M][C] from d_acts [M][C] and the kept gate values gate [M][2C], on rows with rowb >= 0."""
+    pd, ldd, M, Cc = _mat(d_acts)
+    pg, ldg, Mg, Ng = _mat(gate)
+    pp, ldp, Mp, Np = _mat(d_pre)
+    pa, lda, Ma, Na = _mat(acts)
+    if (Mg, Mp, Ma) != (M, M, M) or (Ng, Np, Na) != (2 * Cc, 2 * Cc, Cc) or rowb.numel() < M:
+        raise NativeError("wg_gate_bwd: shape mismatch d_acts=%s gate=%s d_pre=%s acts=%s"
+                          % (tuple(d_acts.shape), tuple(gate.shape), tuple(d_pre.shape), tuple(acts.shape)))
+    _check(load().t2amd_wg_gate_bwd_f32(pd, _i64(ldd), pg, _i64(ldg), ptr(rowb, torch.int32), _i64(M), int(Cc), pp, _i64(ldp),
+                                        pa, _i64(lda), _stream()), "t2amd_wg_gate_bwd_f32")
 
 
 # ----------------------------------------------------------------------------

@@ -4,8 +4,9 @@ denoiser.py's ``Denoiser``) as native HIP passes.
     wg = load_waveglow("waveglow.pt").cuda().eval()
     audio = wg.infer(mel, sigma=0.666)                 # (B, 256 * N) float32
     clean = Denoiser(wg)(audio, strength=0.01)         # (B, 1, T)
-    z, log_s_list, log_det_W_list = wg((mel, audio))   # glow.py's forward: audio -> latents (no backward pass)
+    z, log_s_list, log_det_W_list = wg((mel, audio))   # glow.py's forward: audio -> latents (no grad: see training_loss)
     nats = wg.nll(mel, audio, sigma=1.0)               # (B,) negative log-likelihood per sample, per utterance
+    loss = wg.training_loss(mel, audio, sigma=1.0)     # float32 scalar with a grad_fn; loss.backward() fills p.grad
 
 The module keeps NVIDIA's submodule names (after ``remove_weightnorm``), so ``state_dict()`` keys match glow.py.  Its
 weights are f32 masters; ``precision`` selects the compute of the products: 'fp32' (exact f32 MFMA), 'bf16x3'
@@ -18,7 +19,11 @@ layer (t2amd_wg_layer_f32: the gated dilated product and the residual / skip pro
 allocated once per call, before the flow loop, which does no allocation, copy or host synchronisation.
 The forward direction (``forward``, ``nll``, ``WaveGlowLoss``) runs the same products; between them one flow head per
 flow boundary (t2amd_wg_head_f32: end, affine coupling, log_s, early output, the next flow's 1x1 mix and start) and, for
-the loss, one fixed-order reduction (t2amd_wg_nll_f32).  It has no backward pass: its outputs do not require grad.
+the loss, one fixed-order reduction (t2amd_wg_nll_f32).  ``forward`` has no backward pass: its outputs do not require grad.
+Training goes through ``training_loss``, a torch.autograd.Function over the module's parameters: the same launches with
+the state the backward pass needs kept in one allocation, then per flow boundary one head backward
+(t2amd_wg_head_bwd_f32), per layer one gate backward, the data gradient in one launch (mode 2 of the layer product) and
+the weight gradients on split-K t2amd_gemm_f32.
 The arithmetic is restated in float64 torch by tests/waveglow_ref.py and tests/waveglow_fwd_ref.py; DESIGN.md section 10
 has the layout.
 """
@@ -101,7 +106,7 @@ class Invertible1x1Conv(nn.Module):
         W = torch.linalg.qr(torch.randn(c, c))[0]
         if torch.det(W) < 0:
             W[:, 0] = -W[:, 0]
-        self.conv.weight.data = W.view(c, c, 1)
+        self.conv.weight.data = W.contiguous().view(c, c, 1)
 
 
 class WN(nn.Module):
@@ -212,7 +217,10 @@ class WaveGlow(nn.Module):
 
     # ---- device-side weight layout ------------------------------------------------------------------------------------
     def _packed(self, device):
-        key = (str(device), tuple((p.data_ptr(), p._version) for p in self.parameters()))
+        # torch's version counters see in-place optimiser steps; FusedAdam writes through raw pointers and bumps the
+        # engine's weight generation instead
+        from .engine import _PACK_GEN
+        key = (_PACK_GEN[0], str(device), tuple((p.data_ptr(), p._version) for p in self.parameters()))
         if self._pack is not None and self._pack[0] == key:
             return self._pack[1]
         C, L, G, nm = self.n_channels, self.n_layers, self.n_group, self.n_mel_channels
@@ -234,9 +242,12 @@ class WaveGlow(nn.Module):
                 cw = wn.cond_layer.weight.detach().float().view(2 * C * L, nm, G)
                 f['cond_w'] = cw.permute(0, 2, 1).reshape(2 * C * L, G * nm).contiguous()     # column g n_mel + c
                 f['cond_b'] = wn.cond_layer.bias.detach().float().contiguous()
-                f['in_w'], f['in_b'], f['rs_w'], f['rs_b'] = [], [], [], []
+                f['in_w'], f['in_b'], f['rs_w'], f['rs_b'], f['in_wT'] = [], [], [], [], []
                 for i in range(L):
                     iw = wn.in_layers[i].weight.detach().float().permute(0, 2, 1).reshape(2 * C, 3 * C)
+                    # the data gradient's operand: [c][tap' 2C + n] = W[n][c][2 - tap'] (channel order, taps mirrored)
+                    f['in_wT'].append(wn.in_layers[i].weight.detach().float().flip(2).permute(1, 2, 0)
+                                      .reshape(C, 6 * C).contiguous())
                     f['in_w'].append(iw.index_select(0, gate_perm).contiguous())
                     f['in_b'].append(wn.in_layers[i].bias.detach().float().index_select(0, gate_perm).contiguous())
                     rw = wn.res_skip_layers[i].weight.detach().float()
@@ -249,7 +260,10 @@ class WaveGlow(nn.Module):
                 f['end_w'] = ew.view(ew.shape[0], C).contiguous()
                 f['end_b'] = wn.end.bias.detach().float().contiguous()
                 wc = self.convinv[k].conv.weight.detach()
-                f['winv'] = torch.linalg.inv(wc.double().cpu().view(wc.shape[0], wc.shape[0])).float().contiguous().to(device)
+                winv64 = torch.linalg.inv(wc.double().cpu().view(wc.shape[0], wc.shape[0]))
+                f['winv'] = winv64.float().contiguous().to(device)
+                # d(-sum_b T'_b log det W) / dW / numel = -W^-T / n_group, whatever the batch
+                f['mix_ldg'] = (-winv64.t() / G).float().contiguous().to(device)
                 # the forward direction: the weight itself and log det W (float64 on the host; nan when det W < 0, as
                 # torch.logdet gives)
                 f['mix_w'] = wc.float().view(wc.shape[0], wc.shape[0]).contiguous()
@@ -402,8 +416,9 @@ class WaveGlow(nn.Module):
             pos += R + pad
         return torch.from_numpy(np.concatenate(rowb)), torch.from_numpy(np.concatenate(rowr)), offs, pos
 
-    def _forward(self, spect, audio, lengths, who):
-        """-> (z (B, n_group, T') f32, log_s of all flows (B, sum_k n_half_k, T') f32, rows per utterance (host list))."""
+    def _forward(self, spect, audio, lengths, who, save=False):
+        """-> (z (B, n_group, T') f32, log_s of all flows (B, sum_k n_half_k, T') f32, rows per utterance (host list),
+        the state kept for the backward pass (``save``) or None)."""
         dev = self.upsample.weight.device
         if dev.type != 'cuda' and not nv.validate_only():
             raise nv.NativeError("WaveGlow: move the module to the MI355X first (.cuda()); there is no CPU path")
@@ -439,6 +454,7 @@ class WaveGlow(nn.Module):
         wav = audio.to(device=dev, dtype=torch.float32).contiguous()
 
         cond_g, cnd, h, acts, skip, a_rows, mel_cl = self._workspace(P, B, N, dev)
+        sv = _SavedState(self, P, sum(frames), dev) if save else None
         n_halves = [c // 2 for c in self.flow_channels]
         z = torch.zeros(B, G, Rm, dtype=torch.float32, device=dev)
         log_s = torch.zeros(B, sum(n_halves), Rm, dtype=torch.float32, device=dev)
@@ -453,27 +469,49 @@ class WaveGlow(nn.Module):
         inner = slice(H, P - H)
         cond_r, cnd_r, h_r, acts_r, skip_r, rowb_r = cond_g[inner], cnd[inner], h[inner], acts[inner], skip[inner], rowb[inner]
         fl = pk['flows']
-        nv.wg_head(rowb, rowr, a_rows, G, B, Rm, wave=wav, mix_w=fl[0]['mix_w'], start_w=fl[0]['start_w'],
-                   start_b=fl[0]['start_b'], h=h)
+        if sv is None:
+            nv.wg_head(rowb, rowr, a_rows, G, B, Rm, wave=wav, mix_w=fl[0]['mix_w'], start_w=fl[0]['start_w'],
+                       start_b=fl[0]['start_b'], h=h)
+        else:
+            # the same launches; every layer reads its own image of h and the gate values, skip and head rows are kept
+            fo = 0
+            for b, nf in enumerate(frames):                  # the upsample's operand rows [q][(j, ci)] = mel[q - j][ci]
+                for j in range(min(UP_KERNEL // HOP, nf)):
+                    sv.xc[fo + j:fo + nf, j * nm:(j + 1) * nm].copy_(mel_cl[b * N:b * N + nf - j])
+                fo += nf
+            nv.wg_head(rowb, rowr, a_rows, G, B, Rm, wave=wav, mix_w=fl[0]['mix_w'], start_w=fl[0]['start_w'],
+                       start_b=fl[0]['start_b'], h=sv.hs[0][0], save=sv.heads[0])
         z_off = c_off = 0
         for k in range(self.n_flows):
             f = fl[k]
             nv.gemm(cnd_r, cond_r, f['cond_w'], bias=f['cond_b'], fast=prec)
+            skip_k = skip if sv is None else sv.skip[k]
             for i in range(L):
-                nv.wg_gated(h_r, f['in_w'][i], f['in_b'][i], 2 ** i, cnd_r[:, 2 * C * i:2 * C * (i + 1)], acts_r, prec)
                 last_layer = i == L - 1
-                nv.wg_res_skip(acts_r, f['rs_w'][i], f['rs_b'][i], None if last_layer else h_r, skip_r, i == 0, rowb_r, prec)
+                cnd_i = cnd_r[:, 2 * C * i:2 * C * (i + 1)]
+                if sv is None:
+                    nv.wg_gated(h_r, f['in_w'][i], f['in_b'][i], 2 ** i, cnd_i, acts_r, prec)
+                    nv.wg_res_skip(acts_r, f['rs_w'][i], f['rs_b'][i], None if last_layer else h_r, skip_r, i == 0, rowb_r, prec)
+                else:
+                    h_i = sv.hs[k][i][inner]
+                    nv.wg_gated(h_i, f['in_w'][i], f['in_b'][i], 2 ** i, cnd_i, acts_r, prec, gate=sv.gate[k][i][inner])
+                    nv.wg_res_skip(acts_r, f['rs_w'][i], f['rs_b'][i], None if last_layer else h_i, skip_k[inner], i == 0,
+                                   rowb_r, prec, h_out=None if last_layer else sv.hs[k][i + 1][inner])
             last = k == self.n_flows - 1
             n_in = self.flow_channels[k]
             n_emit = n_in if last else n_in - self.flow_channels[k + 1]
             nxt = None if last else fl[k + 1]
-            nv.wg_head(rowb, rowr, a_rows, G, B, Rm, skip=skip, end_w=f['end_w'], end_b=f['end_b'],
+            h_next = None if last else (h if sv is None else sv.hs[k + 1][0])
+            nv.wg_head(rowb, rowr, a_rows, G, B, Rm, skip=skip_k, end_w=f['end_w'], end_b=f['end_b'],
                        log_s=log_s[:, c_off:c_off + n_halves[k]], z=z if n_emit else None, z_off=z_off, n_emit=n_emit,
                        mix_w=nxt['mix_w'] if nxt else None, start_w=nxt['start_w'] if nxt else None,
-                       start_b=nxt['start_b'] if nxt else None, h=h if nxt else None)
+                       start_b=nxt['start_b'] if nxt else None, h=h_next, **({} if sv is None else {'save': sv.heads[k + 1]}))
             z_off += n_emit
             c_off += n_halves[k]
-        return z, log_s, rows
+        if sv is not None:
+            sv.keep(pk=pk, prec=prec, rowb=rowb, rowr=rowr, offs=offs, frames=frames, rows=rows, cond_g=cond_g, log_s=log_s,
+                    B=B, Rm=Rm)
+        return z, log_s, rows, sv
 
     def _split_log_s(self, log_s):
         out, c = [], 0
@@ -490,10 +528,11 @@ class WaveGlow(nn.Module):
         buffer); log_det_W_list[k] = B T' logdet(W_k), a float32 scalar (nan when det W_k < 0).
         ``lengths``: samples per utterance (ragged: each utterance computed as if alone, z and log_s zero beyond T'_b,
         log_det_W_list[k] = sum_b T'_b logdet(W_k)).
-        There is no backward pass: the outputs do not require grad, whatever the inputs and the parameters do.
+        This entry has no backward pass: the outputs do not require grad, whatever the inputs and the parameters do
+        (``training_loss`` is the differentiable one).
         After ``.half()``: bf16 compute, z and log_s float16 (log_det_W_list stays float32: it grows with B T')."""
         spect, audio = forward_input
-        z, log_s, rows = self._forward(spect, audio, lengths, "forward")
+        z, log_s, rows, _ = self._forward(spect, audio, lengths, "forward")
         logdet = self._packed(z.device)['logdet']
         ld = torch.tensor([sum(rows) * v for v in logdet], dtype=torch.float32, device=z.device)
         if self.half_io:
@@ -504,7 +543,7 @@ class WaveGlow(nn.Module):
     def nll(self, spect, audio, sigma=1.0, lengths=None):
         """(B,) float32: the value ``WaveGlowLoss(sigma)`` gives for each utterance alone (nats per sample), from one
         ``forward`` of the (ragged) batch and the reduction kernel."""
-        z, log_s, rows = self._forward(spect, audio, lengths, "nll")
+        z, log_s, rows, _ = self._forward(spect, audio, lengths, "nll")
         dev = z.device
         sums = _nll_sums(z, log_s, torch.tensor(rows, dtype=torch.int32, device=dev))
         logdet = self._packed(dev)['logdet']
@@ -513,6 +552,188 @@ class WaveGlow(nn.Module):
         ld = torch.tensor(ld, dtype=torch.float64, device=dev)
         numel = torch.tensor([self.n_group * r for r in rows], dtype=torch.float64, device=dev)
         return ((sums[:, 0] / (2.0 * sigma * sigma) - sums[:, 1] - ld) / numel).float()
+
+    # ---- training: the loss with a backward pass ------------------------------------------------------------------------
+    def saved_state_bytes(self, P, n_frames=0):
+        """Bytes ``training_loss`` keeps between its forward and its backward for P packed rows: per flow and layer the
+        layer's input image h (C floats per row) and the two gate values (2C), per flow skip (C), per flow boundary the
+        rows before and after the 1x1 mix (2 n_group), and the upsample's operand rows:
+        4 (P (n_flows (3 C L + C) + 2 n_group (n_flows + 1)) + 4 n_mel n_frames)."""
+        C, L, G, F = self.n_channels, self.n_layers, self.n_group, self.n_flows
+        return 4 * (P * (F * (3 * C * L + C) + 2 * G * (F + 1)) + (UP_KERNEL // HOP) * self.n_mel_channels * n_frames)
+
+    def _loss_value(self, z, log_s, rows, sigma):
+        """WaveGlowLoss's arithmetic over the real rows: (sum z^2 / (2 sigma^2) - sum log_s - sum_k sum_b T'_b log det W_k)
+        / (n_group sum_b T'_b), the sums in float64 on the reduction kernel."""
+        dev = z.device
+        sums = _nll_sums(z, log_s, torch.tensor(rows, dtype=torch.int32, device=dev)).sum(0)
+        logdet = self._packed(dev)['logdet']
+        ld = torch.tensor([sum(rows) * v for v in logdet], dtype=torch.float32, device=dev).double().sum()
+        return ((sums[0] / (2.0 * sigma * sigma) - sums[1] - ld) / (self.n_group * sum(rows))).float()
+
+    def training_loss(self, spect, audio, sigma=1.0, lengths=None):
+        """The training loss of glow.py, a float32 scalar with a backward pass: ``WaveGlowLoss(sigma)(forward((spect,
+        audio)))`` for a full batch (bit for bit: the same launches).  With ``lengths`` (samples per utterance, the rules
+        of ``forward``: multiples of n_group, at most 256 N) it is the sum of the per-utterance negative log-likelihoods
+        divided by the number of REAL samples sum_b T_b -- the mean over what was scored, not over the padding.
+
+        ``loss.backward()`` gives every parameter of the module that requires grad its float32 gradient, in the
+        parameter's own layout, multiplied by the upstream scalar and added into an existing ``.grad``.  The parameters are
+        the folded weights (``fold_weight_norm``), so these are gradients with respect to the folded weights; training
+        under the g / v weight-norm parametrisation is not supported.  ``spect`` and ``audio`` get no gradient: an input
+        that requires grad is refused.  ``precision`` selects the compute of the products in both directions; the
+        weights and the gradients are float32 in all three (after ``.half()``: bf16 compute).  Under ``torch.no_grad()``
+        (or when no parameter requires grad) the value is the same and nothing is kept.
+
+        Between forward and backward the call keeps ``saved_state_bytes(P, frames)`` bytes in one allocation: 3 C L + C
+        floats per packed row and flow (C = 256, L = 8, 12 flows, B = 12 x T = 16000: 26 k rows, 7.7 GB).  Every layer's
+        input and gate values are stored rather than recomputed: recomputing a flow's WN would cost a fourth forward per
+        step on a part whose memory is not the constraint.  A state that does not fit is refused before anything runs."""
+        for name, t in (("mels", spect), ("audio", audio)):
+            if torch.is_tensor(t) and t.requires_grad:
+                raise ValueError("WaveGlow.training_loss: the %s require grad, but gradients with respect to the inputs are "
+                                 "not computed (detach them)" % name)
+        params = list(self.parameters())
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return _TrainingLoss.apply(self, spect, audio, float(sigma), lengths, *params)
+        with torch.no_grad():
+            z, log_s, rows, _ = self._forward(spect, audio, lengths, "training_loss")
+            return self._loss_value(z, log_s, rows, float(sigma))
+
+    def _grad_layout(self):
+        """(floats, {parameter name: (offset, shape)}, [(offset, floats) of head call j]) of the flat gradient buffer.  The
+        small gradients of one head call are contiguous, in the order the head backward sums them: end of the flow it
+        closes (weight, bias), then start (weight, bias) and the 1x1 mix of the flow it opens."""
+        C, L, F = self.n_channels, self.n_layers, self.n_flows
+        lay, calls, o = {}, [], 0
+
+        def put(name, shape):
+            nonlocal o
+            lay[name] = (o, tuple(shape))
+            o += int(np.prod(shape))
+
+        for j in range(F + 1):
+            o0 = o
+            if j > 0:
+                n_in = self.flow_channels[j - 1]
+                put('WN.%d.end.weight' % (j - 1), (n_in, C, 1))
+                put('WN.%d.end.bias' % (j - 1), (n_in,))
+            if j < F:
+                n = self.flow_channels[j]
+                put('WN.%d.start.weight' % j, (C, n // 2, 1))
+                put('WN.%d.start.bias' % j, (C,))
+                put('convinv.%d.conv.weight' % j, (n, n, 1))
+            calls.append((o0, o - o0))
+        o = -(-o // 4) * 4
+        for name, p in self.named_parameters():
+            if name not in lay:
+                put(name, p.shape)
+                o = -(-o // 4) * 4
+        return o, lay, calls
+
+    def _backward(self, sv, sigma, upstream):
+        """The backward pass over the kept state -> {parameter name: gradient (a view of one flat float32 buffer)}."""
+        C, L, G, nm, F, H = self.n_channels, self.n_layers, self.n_group, self.n_mel_channels, self.n_flows, self.halo()
+        pk, prec, rowb, rowr, P, B, Rm = sv.pk, sv.prec, sv.rowb, sv.rowr, sv.P, sv.B, sv.Rm
+        dev = rowb.device
+        fl = pk['flows']
+        taps = UP_KERNEL // HOP
+        numel = float(G * sum(sv.rows))
+        c1, c2 = 1.0 / (sigma * sigma * numel), -1.0 / numel
+        total, lay, calls = self._grad_layout()
+        gout = torch.empty(total, dtype=torch.float32, device=dev)
+        gv = {name: gout[o:o + int(np.prod(shape))].view(shape) for name, (o, shape) in lay.items()}
+
+        # one workspace: [d_cnd | dcat = (dh, d_skip) | acts | dA] zeroed (their halo rows are read as zero), then the rest
+        M = P - 2 * H
+        sk = [_splitk(2 * C, C, M), _splitk(2 * C * L, G * nm, M)]
+        nblk = -(-P // nv.wg_head_bwd_rows())
+        npart = max(n for _, n in calls)
+        wsN = max(2 * C * L, G * nm)
+        sizes = [P * 2 * C * L, P * 2 * C, P * C, P * G,
+                 P * G * nm, P * C, max(sk[0] * 2 * C * C, sk[1] * 2 * C * L * G * nm), nblk * npart,
+                 2 * C * 3 * C, 2 * C * L * G * nm, HOP * nm * taps * nm, 2 * 2 * 64 * wsN]
+        sizes = [-(-n // 4) * 4 for n in sizes]
+        bw = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        parts, o = [], 0
+        for n in sizes:
+            parts.append(bw[o:o + n])
+            o += n
+        bw[:sum(sizes[:4])].zero_()
+        d_cnd = parts[0][:P * 2 * C * L].view(P, 2 * C * L)
+        dcat = parts[1][:P * 2 * C].view(P, 2 * C)
+        actsb = parts[2][:P * C].view(P, C)
+        dA = parts[3][:P * G].view(P, G)
+        d_cond_g = parts[4][:P * G * nm].view(P, G * nm)
+        d_acts = parts[5][:P * C].view(P, C)
+        wpart, hpart = parts[6], parts[7]
+        g_in = parts[8][:6 * C * C].view(2 * C, 3 * C)
+        g_cond = parts[9][:2 * C * L * G * nm].view(2 * C * L, G * nm)
+        g_up = parts[10][:HOP * nm * taps * nm].view(HOP * nm, taps * nm)
+        ws64 = parts[11].view(torch.float64)
+        inner = slice(H, P - H)
+        rowb_r = rowb[inner]
+        dh, dskip = dcat[:, :C], dcat[:, C:]
+        n_halves = [c // 2 for c in self.flow_channels]
+        c_offs = [sum(n_halves[:k]) for k in range(F)]
+
+        def head_bwd(j):
+            """Backward of head call j: it closed flow j - 1 and opened flow j."""
+            k = j - 1
+            n_cur = self.flow_channels[k] if j > 0 else G
+            n_out = self.flow_channels[j] if j < F else 0
+            kw = {}
+            if j > 0:
+                kw.update(skip=sv.skip[k], end_w=fl[k]['end_w'], log_s=sv.log_s[:, c_offs[k]:c_offs[k] + n_halves[k]],
+                          a_in=sv.heads[k][:, G:], dA=dA, d_skip=dskip)
+            if j < F:
+                kw.update(dA=dA, dh0=dh, mix_w=fl[j]['mix_w'], start_w=fl[j]['start_w'], a_sv=sv.heads[j][:, G:])
+            nb, n = nv.wg_head_bwd(rowb, rowr, G, B, Rm, c1, c2, sv.heads[j][:, :G], hpart, n_emit=n_cur - n_out, **kw)
+            o, cnt = calls[j]
+            nv.wg_partial_sum(hpart, nb, n, gout[o:o + cnt])
+            if j < F:
+                gv['convinv.%d.conv.weight' % j].view(n_out, n_out).add_(fl[j]['mix_ldg'])
+
+        head_bwd(F)
+        for k in reversed(range(F)):
+            f = fl[k]
+            pre = 'WN.%d.' % k
+            for i in reversed(range(L)):
+                last_layer = i == L - 1
+                dout = dskip[inner] if last_layer else dcat[inner]                 # gradient of [residual | skip]
+                d_pre = d_cnd[inner][:, 2 * C * i:2 * C * (i + 1)]
+                nv.gemm(d_acts[inner], dout, f['rs_w'][i], b_kn=True, fast=prec)
+                nv.wg_gate_bwd(d_acts[inner], sv.gate[k][i][inner], rowb_r, d_pre, actsb[inner])
+                g_rs = gv[pre + 'res_skip_layers.%d.weight' % i]
+                _wgrad(g_rs.view(g_rs.shape[0], C), dout, actsb[inner], prec, wpart)
+                nv.colsum(dout, ws64, gv[pre + 'res_skip_layers.%d.bias' % i])
+                h_i = sv.hs[k][i]
+                d = 2 ** i
+                for tap in range(3):
+                    _wgrad(g_in[:, tap * C:(tap + 1) * C], d_pre, h_i[H + (tap - 1) * d:P - H + (tap - 1) * d], prec, wpart)
+                gv[pre + 'in_layers.%d.weight' % i].copy_(g_in.view(2 * C, 3, C).permute(0, 2, 1))
+                nv.wg_dgrad(d_pre, f['in_wT'][i], d, dh[inner], last_layer, rowb_r, prec)
+            # the cond layer: its bias gradient is every in-layer bias gradient of the flow, side by side
+            g_cb = gv[pre + 'cond_layer.bias']
+            nv.colsum(d_cnd[inner], ws64, g_cb)
+            for i in range(L):
+                gv[pre + 'in_layers.%d.bias' % i].copy_(g_cb[2 * C * i:2 * C * (i + 1)])
+            _wgrad(g_cond, d_cnd[inner], sv.cond_g[inner], prec, wpart)
+            gv[pre + 'cond_layer.weight'].view(2 * C * L, nm, G).copy_(g_cond.view(2 * C * L, G, nm).permute(0, 2, 1))
+            nv.gemm(d_cond_g[inner], d_cnd[inner], f['cond_w'], b_kn=True, accumulate=k != F - 1, fast=prec)
+            head_bwd(k)
+
+        # the upsample: out[q][p n_mel + co] = sum_(j, ci) mel[q - j][ci] W[ci][co][p + 256 j] + b[co]
+        spf = HOP // G
+        fo = 0
+        for b, nf in enumerate(sv.frames):
+            dst = d_cond_g[sv.offs[b]:sv.offs[b] + spf * nf].view(nf, HOP * nm)
+            nv.gemm(g_up, dst, sv.xc[fo:fo + nf], a_km=True, b_kn=True, accumulate=b > 0, fast=prec)
+            fo += nf
+        gv['upsample.weight'].view(nm, nm, taps, HOP).copy_(g_up.view(HOP, nm, taps, nm).permute(3, 1, 2, 0))
+        nv.colsum(d_cond_g[inner].reshape(-1, nm), ws64, gv['upsample.bias'])
+        gout.mul_(upstream.to(device=dev, dtype=torch.float32))
+        return gv
 
 
 def _nll_sums(z, log_s, rows):
@@ -523,6 +744,73 @@ def _nll_sums(z, log_s, rows):
     out = buf[B * nchunk * 2:].view(B, 2)
     nv.wg_nll(z, log_s, rows, buf[:B * nchunk * 2], out)
     return out
+
+
+def _splitk(M, N, K):
+    """Split count of a weight-gradient product [M][N] over K rows: about two workgroups of 128 x 128 per compute unit,
+    at least 512 rows per slice."""
+    tiles = -(-M // 128) * -(-N // 128)
+    return max(1, min(-(-512 // tiles), K // 512, 64))
+
+
+def _wgrad(out, A, Bm, prec, partials):
+    """out [M][N] = A^T . Bm over the rows of A [K][M] and Bm [K][N] (halo rows are zero in one of them), split-K in a
+    fixed order."""
+    K, M = A.shape
+    s = _splitk(M, Bm.shape[1], K)
+    if s == 1:
+        nv.gemm(out, A, Bm, a_km=True, b_kn=True, fast=prec)
+    else:
+        nv.gemm(out, A, Bm, a_km=True, b_kn=True, splitk=s, partials=partials, fast=prec)
+        nv.splitk_reduce2d(partials, s, out)
+
+
+class _SavedState:
+    """What ``training_loss`` keeps for its backward pass, in one allocation (``WaveGlow.saved_state_bytes``):
+    hs[k][i] [P][C] the input image of layer i of flow k (zero halos), gate[k][i] [P][2C] its tanh | sigmoid values,
+    skip[k] [P][C], heads[j] [P][2 n_group] the rows before | after the 1x1 mix of head call j, xc the upsample's operand."""
+
+    def __init__(self, wg, P, n_frames, dev):
+        C, L, G, F, nm = wg.n_channels, wg.n_layers, wg.n_group, wg.n_flows, wg.n_mel_channels
+        need = wg.saved_state_bytes(P, n_frames)
+        if dev.type == 'cuda':
+            free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+            if need > free:
+                raise nv.NativeError("WaveGlow.training_loss: the state kept for the backward pass needs %.2f GB (%d packed "
+                                     "rows x %d flows x (3 C L + C) floats) and %.2f GB are free; use a smaller batch or "
+                                     "shorter segments" % (need / 1e9, P, F, free / 1e9))
+        sizes = [F * L * P * C, F * L * P * 2 * C, F * P * C, (F + 1) * P * 2 * G, n_frames * (UP_KERNEL // HOP) * nm]
+        buf = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        assert buf.numel() * 4 == need
+        o = np.cumsum([0] + sizes)
+        self.hs = buf[o[0]:o[1]].view(F, L, P, C)
+        self.gate = buf[o[1]:o[2]].view(F, L, P, 2 * C)
+        self.skip = buf[o[2]:o[3]].view(F, P, C)
+        self.heads = buf[o[3]:o[4]].view(F + 1, P, 2 * G)
+        self.xc = buf[o[4]:o[5]].view(n_frames, (UP_KERNEL // HOP) * nm)
+        self.hs.zero_()
+        self.xc.zero_()
+        self.P, self.bytes = P, need
+
+    def keep(self, **kw):
+        self.__dict__.update(kw)
+
+
+class _TrainingLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, wg, spect, audio, sigma, lengths, *params):
+        z, log_s, rows, sv = wg._forward(spect, audio, lengths, "training_loss", save=True)
+        ctx.wg, ctx.sv, ctx.sigma = wg, sv, sigma
+        ctx.names = [n for n, _ in wg.named_parameters()]
+        return wg._loss_value(z, log_s, rows, sigma)
+
+    @staticmethod
+    def backward(ctx, upstream):
+        if ctx.sv is None:
+            raise RuntimeError("WaveGlow.training_loss: backward was already run; the kept state is freed by the first one")
+        gv = ctx.wg._backward(ctx.sv, ctx.sigma, upstream)
+        ctx.sv = None
+        return (None,) * 5 + tuple(gv[n] if need else None for n, need in zip(ctx.names, ctx.needs_input_grad[5:]))
 
 
 def _one_buffer(tensors):
@@ -548,7 +836,7 @@ def _one_buffer(tensors):
 class WaveGlowLoss(nn.Module):
     """glow.py's WaveGlowLoss: ``(sum(z^2) / (2 sigma^2) - sum_k sum(log_s_k) - sum_k log_det_W_k) / z.numel()`` of the
     output of ``WaveGlow.forward``, a float32 scalar.  The two sums run on the reduction kernel (fixed order, float64
-    accumulation).  No backward pass: the result does not require grad."""
+    accumulation).  No backward pass: the result does not require grad (``WaveGlow.training_loss`` is the loss that trains)."""
 
     def __init__(self, sigma=1.0):
         super().__init__()
