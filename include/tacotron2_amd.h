@@ -1048,6 +1048,21 @@ int t2amd_wg_partial_sum_f32(const float* partial, long long nblk, long long n, 
  * d_pre[m][c] = d_acts[m][c] s (1 - t^2);  d_pre[m][C + c] = d_acts[m][c] t s (1 - s);  acts[m][c] = t s. */
 int t2amd_wg_gate_bwd_f32(const float* d_acts, long long ldd, const float* gate, long long ldg, const int* rowb, long long M,
                           int C, float* d_pre, long long ldp, float* acts, long long lda, void* stream);
+/* Weight norm over a segment table (csrc/waveglow_wn.hip), one launch for all weight-normed tensors of a WaveGlow.
+ * table: int64 [n_seg][6] on the device, per tensor {off, goff, dwoff, rows, len, first}: offsets in floats of the tensor
+ * in the v / w / dv buffers (off), of its rows in the g / norm / dg buffers (goff) and of its gradient in the dw buffer
+ * (dwoff), its rows and floats per row, and its first work unit (one unit per row when len >
+ * t2amd_wg_weight_norm_short(), else one per 64 rows; counted through the table, n_units in all).  The caller
+ * guarantees that every line lies inside the buffers; the bases are 16-byte aligned.
+ *   fold:     n = sqrt(sum_j v[r][j]^2);  w[r][j] = v[r][j] (g[r] / n);  norm[r] = n
+ *   backward: d = sum_j dw[r][j] v[r][j];  dg[r] = scale d / n;  dv[r][j] = scale (g[r] / n) (dw[r][j] - v[r][j] d / n^2)
+ * The sum order of a row depends on len alone (fixed in-wave reduction, no atomics). */
+int t2amd_wg_weight_norm_short(void);
+int t2amd_wg_weight_norm_f32(const long long* table, int n_seg, long long n_units, const float* v_base, const float* g_base,
+                             float* w_base, float* norm_base, void* stream);
+int t2amd_wg_weight_norm_bwd_f32(const long long* table, int n_seg, long long n_units, const float* dw_base,
+                                 const float* v_base, const float* g_base, const float* norm_base, float* dg_base,
+                                 float* dv_base, float scale, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Optimiser step: global-norm clipping + Adam over all parameter

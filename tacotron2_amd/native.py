@@ -290,6 +290,7 @@ SYMBOLS = [
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
     "t2amd_wg_layer_train_f32", "t2amd_wg_head_save_f32", "t2amd_wg_head_bwd_rows", "t2amd_wg_head_bwd_f32",
     "t2amd_wg_partial_sum_f32", "t2amd_wg_gate_bwd_f32",
+    "t2amd_wg_weight_norm_short", "t2amd_wg_weight_norm_f32", "t2amd_wg_weight_norm_bwd_f32",
     "t2amd_optim_chunk", "t2amd_grad_norm_f32", "t2amd_adam_step_f32",
     "t2amd_decoder_persist_mailbox_bytes", "t2amd_decoder_persist_supported", "t2amd_decoder_infer_persistent_f32",
     "t2amd_loss_workspace_doubles", "t2amd_tacotron2_loss_fwd_f32", "t2amd_tacotron2_loss_bwd_f32",
@@ -406,6 +407,9 @@ def _argtypes():
                                   _P, _L, _P, _P, _L, _I, _I, _L, _F, _F, _P],
         "t2amd_wg_partial_sum_f32": [_P, _L, _L, _P, _P],
         "t2amd_wg_gate_bwd_f32": [_P, _L, _P, _L, _P, _L, _I, _P, _L, _P, _L, _P],
+        "t2amd_wg_weight_norm_short": [],
+        "t2amd_wg_weight_norm_f32": [_P, _I, _L, _P, _P, _P, _P, _P],
+        "t2amd_wg_weight_norm_bwd_f32": [_P, _I, _L, _P, _P, _P, _P, _P, _P, _F, _P],
         "t2amd_optim_chunk": [],
         "t2amd_grad_norm_f32": [pt(TensorList), _F, _P, _P, _P],
         "t2amd_adam_step_f32": [pt(TensorList), pt(AdamHyper), _P, _P],
@@ -1979,6 +1983,73 @@ def wg_gate_bwd(d_acts, gate, rowb, d_pre, acts):
                           % (tuple(d_acts.shape), tuple(gate.shape), tuple(d_pre.shape), tuple(acts.shape)))
     _check(load().t2amd_wg_gate_bwd_f32(pd, _i64(ldd), pg, _i64(ldg), ptr(rowb, torch.int32), _i64(M), int(Cc), pp, _i64(ldp),
                                         pa, _i64(lda), _stream()), "t2amd_wg_gate_bwd_f32")
+
+
+WG_WN_SHORT = 4        # rows of at most this many floats are folded one per lane, 64 per work unit (WGN_SHORT of the kernels)
+
+
+def wg_weight_norm_table(segments):
+    """-> (int64 [n][6] host table, work units) for ``segments`` = [(off, goff, dwoff, rows, len)]: the layout
+    t2amd_wg_weight_norm_f32 reads (include/tacotron2_amd.h), the work units counted through the table."""
+    short = WG_WN_SHORT
+    lines, first = [], 0
+    for off, goff, dwoff, rows, ln in segments:
+        lines.append([int(off), int(goff), int(dwoff), int(rows), int(ln), first])
+        first += -(-int(rows) // 64) if ln <= short else int(rows)
+    return torch.tensor(lines, dtype=torch.int64).view(-1, 6), first
+
+
+def _wn_table_check(who, table, host, n_units, big, small, dw=None):
+    """The kernels trust the table: every line is checked here, on the host copy, against the buffers it addresses."""
+    if host.dtype != torch.int64 or host.dim() != 2 or host.shape[1] != 6 or host.shape[0] < 1 or host.is_cuda:
+        raise NativeError("%s: the host table must be an int64 [n][6] CPU tensor" % who)
+    if table.dtype != torch.int64 or tuple(table.shape) != tuple(host.shape) or not table.is_contiguous():
+        raise NativeError("%s: the device table must be a contiguous int64 tensor of the host table's shape" % who)
+    short = WG_WN_SHORT
+    if int(load().t2amd_wg_weight_norm_short()) != short:
+        raise NativeError("%s: the library folds rows of up to %d floats per lane, native.py expects %d"
+                          % (who, load().t2amd_wg_weight_norm_short(), short))
+    first = 0
+    for s, (off, goff, dwoff, rows, ln, f) in enumerate(host.tolist()):
+        if rows < 1 or ln < 1 or off < 0 or goff < 0 or dwoff < 0:
+            raise NativeError("%s: table line %d: bad rows / len / offsets" % (who, s))
+        if f != first:
+            raise NativeError("%s: table line %d starts at work unit %d, expected %d" % (who, s, f, first))
+        first += -(-rows // 64) if ln <= short else rows
+        if ln > short and ln % 4 == 0 and (off % 4 or (dw is not None and dwoff % 4)):
+            raise NativeError("%s: table line %d: rows of a multiple of 4 floats must start at a multiple of 4 floats"
+                              % (who, s))
+        for t in big:
+            if off + rows * ln > t.numel():
+                raise NativeError("%s: table line %d reaches float %d of a buffer of %d" % (who, s, off + rows * ln, t.numel()))
+        for t in small:
+            if goff + rows > t.numel():
+                raise NativeError("%s: table line %d reaches row %d of a buffer of %d" % (who, s, goff + rows, t.numel()))
+        if dw is not None and dwoff + rows * ln > dw.numel():
+            raise NativeError("%s: table line %d reaches float %d of a gradient buffer of %d"
+                              % (who, s, dwoff + rows * ln, dw.numel()))
+    if first != n_units:
+        raise NativeError("%s: the table holds %d work units, not %d" % (who, first, n_units))
+    for t in list(big) + list(small) + ([dw] if dw is not None else []):
+        if t.dim() != 1:
+            raise NativeError("%s: the buffers are flat (1-D) tensors" % who)
+        _fullc(t)
+
+
+def wg_weight_norm(table, host, n_units, v, g, w, norm):
+    """The fold of every tensor of the table in one launch: w = v g / ||v|| per row, norm = ||v|| (flat f32 buffers;
+    ``table`` on the device, ``host`` its CPU copy, both from ``wg_weight_norm_table``)."""
+    _wn_table_check("wg_weight_norm", table, host, n_units, (v, w), (g, norm))
+    _check(load().t2amd_wg_weight_norm_f32(ptr(table, torch.int64), int(host.shape[0]), _i64(n_units), ptr(v), ptr(g), ptr(w),
+                                           ptr(norm), _stream()), "t2amd_wg_weight_norm_f32")
+
+
+def wg_weight_norm_bwd(table, host, n_units, dw, v, g, norm, dg, dv, scale=1.0):
+    """The fold's backward in one launch: dg, dv (laid out like g, v) from dw (at the table's dwoff), times ``scale``."""
+    _wn_table_check("wg_weight_norm_bwd", table, host, n_units, (v, dv), (g, norm, dg), dw=dw)
+    _check(load().t2amd_wg_weight_norm_bwd_f32(ptr(table, torch.int64), int(host.shape[0]), _i64(n_units), ptr(dw), ptr(v),
+                                               ptr(g), ptr(norm), ptr(dg), ptr(dv), _F(float(scale)), _stream()),
+           "t2amd_wg_weight_norm_bwd_f32")
 
 
 # ----------------------------------------------------------------------------

@@ -7,6 +7,7 @@ denoiser.py's ``Denoiser``) as native HIP passes.
     z, log_s_list, log_det_W_list = wg((mel, audio))   # glow.py's forward: audio -> latents (no grad: see training_loss)
     nats = wg.nll(mel, audio, sigma=1.0)               # (B,) negative log-likelihood per sample, per utterance
     loss = wg.training_loss(mel, audio, sigma=1.0)     # float32 scalar with a grad_fn; loss.backward() fills p.grad
+    wg.apply_weight_norm()                             # glow.py's training parametrisation: weight_g / weight_v
 
 The module keeps NVIDIA's submodule names (after ``remove_weightnorm``), so ``state_dict()`` keys match glow.py.  Its
 weights are f32 masters; ``precision`` selects the compute of the products: 'fp32' (exact f32 MFMA), 'bf16x3'
@@ -24,6 +25,10 @@ Training goes through ``training_loss``, a torch.autograd.Function over the modu
 the state the backward pass needs kept in one allocation, then per flow boundary one head backward
 (t2amd_wg_head_bwd_f32), per layer one gate backward, the data gradient in one launch (mode 2 of the layer product) and
 the weight gradients on split-K t2amd_gemm_f32.
+Under weight norm (``WaveGlow(weight_norm=True)`` / ``apply_weight_norm``: glow.py's own training parametrisation, the keys
+of NVIDIA's training checkpoints) start, in_layers, res_skip_layers and cond_layer own ``weight_g`` / ``weight_v``; all of
+them are folded into one flat buffer by one launch per weight version (t2amd_wg_weight_norm_f32) and their gradients
+come from one more launch per backward pass (t2amd_wg_weight_norm_bwd_f32); everything else is the folded module's path.
 The arithmetic is restated in float64 torch by tests/waveglow_ref.py and tests/waveglow_fwd_ref.py; DESIGN.md section 10
 has the layout.
 """
@@ -130,7 +135,8 @@ class WN(nn.Module):
 
 
 class WaveGlow(nn.Module):
-    def __init__(self, n_mel_channels, n_flows, n_group, n_early_every, n_early_size, WN_config, precision='fp32'):
+    def __init__(self, n_mel_channels, n_flows, n_group, n_early_every, n_early_size, WN_config, precision='fp32',
+                 weight_norm=False):
         super().__init__()
         C, L, ks = WN_config['n_channels'], WN_config['n_layers'], WN_config['kernel_size']
         if ks != 3:
@@ -166,6 +172,10 @@ class WaveGlow(nn.Module):
         self.precision = precision
         self.half_io = False
         self._pack = None
+        self.weight_norm = False
+        self._wn = None
+        if weight_norm:
+            self.apply_weight_norm()
 
     # ---- precision / dtype -------------------------------------------------------------------------------------------
     @property
@@ -190,7 +200,15 @@ class WaveGlow(nn.Module):
 
     # ---- loading ------------------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict, strict=True, assign=False):
-        sd = fold_weight_norm(dict(state_dict))
+        """A folded module folds a weight-normed state dict on load; a weight-normed module takes ``weight_g`` /
+        ``weight_v`` as they are and refuses a folded state dict."""
+        sd = dict(state_dict)
+        if self.weight_norm:
+            if not any(k.endswith('.weight_g') for k in sd):
+                raise ValueError("WaveGlow: the module is weight-normed (weight_g / weight_v) and the state dict is folded: "
+                                 "load it into a folded module and call apply_weight_norm(), or remove_weight_norm() first")
+        else:
+            sd = fold_weight_norm(sd)
         cfg = config_from_state_dict(sd)
         mine = dict(n_mel_channels=self.n_mel_channels, n_flows=self.n_flows, n_group=self.n_group,
                     WN_config=dict(n_layers=self.n_layers, n_channels=self.n_channels, kernel_size=3))
@@ -202,18 +220,146 @@ class WaveGlow(nn.Module):
         return super().load_state_dict(sd, strict=strict, assign=assign)
 
     @classmethod
-    def from_state_dict(cls, state_dict, precision='fp32'):
-        sd = fold_weight_norm(dict(state_dict))
+    def from_state_dict(cls, state_dict, precision='fp32', weight_norm=False):
+        """``weight_norm=False`` (default) folds ``weight_g`` / ``weight_v``; ``weight_norm=True`` gives a weight-normed
+        module that keeps them as they are (a folded source gets ``v = w``, ``g = ||w||``)."""
+        sd = dict(state_dict)
+        if weight_norm and any(k.endswith('.weight_g') for k in sd):
+            m = cls(precision=precision, weight_norm=True, **config_from_state_dict(sd))
+            m.load_state_dict(sd)
+            return m
+        sd = fold_weight_norm(sd)
         m = cls(precision=precision, **config_from_state_dict(sd))
         m.load_state_dict(sd)
-        return m
+        return m.apply_weight_norm() if weight_norm else m
 
     @classmethod
-    def from_module(cls, module, precision='fp32'):
+    def from_module(cls, module, precision='fp32', weight_norm=False):
         """Adopt a loaded NVIDIA WaveGlow (weight-normed or not): its weights are read once."""
         with torch.no_grad():
             sd = {k: v.detach().float().cpu() for k, v in module.state_dict().items()}
-        return cls.from_state_dict(sd, precision=precision)
+        return cls.from_state_dict(sd, precision=precision, weight_norm=weight_norm)
+
+    # ---- the g / v parametrisation ------------------------------------------------------------------------------------
+    def _wn_modules(self):
+        """(name, conv) of the layers glow.py wraps in weight norm, in table order."""
+        for k, wn in enumerate(self.WN):
+            pre = 'WN.%d.' % k
+            yield pre + 'start', wn.start
+            for i in range(self.n_layers):
+                yield pre + 'in_layers.%d' % i, wn.in_layers[i]
+            for i in range(self.n_layers):
+                yield pre + 'res_skip_layers.%d' % i, wn.res_skip_layers[i]
+            yield pre + 'cond_layer', wn.cond_layer
+
+    def _folded_shapes(self):
+        """[(name, shape)] of the parameters of the folded form, in ``named_parameters`` order."""
+        out = []
+        for name, p in self.named_parameters():
+            if name.endswith('.weight_g'):
+                continue
+            out.append((name[:-2], tuple(p.shape)) if name.endswith('.weight_v') else (name, tuple(p.shape)))
+        return out
+
+    def apply_weight_norm(self):
+        """Switch to glow.py's training parametrisation in place: start, in_layers, res_skip_layers and cond_layer of
+        every flow own ``weight_g`` (C_out, 1, 1) and ``weight_v`` instead of ``weight``, with ``v = w`` and ``g = ||w||``
+        per output channel (what ``torch.nn.utils.weight_norm`` does), so the function computed does not change.
+        ``state_dict()`` then has the keys of NVIDIA's training checkpoints."""
+        if self.weight_norm:
+            return self
+        with torch.no_grad():
+            for _, m in self._wn_modules():
+                w = m.weight
+                g = nn.Parameter(torch.norm_except_dim(w.detach(), 2, 0), requires_grad=w.requires_grad)
+                v = nn.Parameter(w.detach().clone(), requires_grad=w.requires_grad)
+                del m._parameters['weight']
+                m.register_parameter('weight_g', g)
+                m.register_parameter('weight_v', v)
+                m.weight = w.detach()                  # a plain attribute from here on: a slice of the fold's output
+        self.weight_norm, self._pack = True, None
+        self._wn_flatten()
+        return self
+
+    def remove_weight_norm(self):
+        """Back to the folded form in place: ``weight = g v / ||v||``, computed as ``torch.nn.utils.remove_weight_norm``
+        does (``fold_weight_norm``)."""
+        if not self.weight_norm:
+            return self
+        with torch.no_grad():
+            for _, m in self._wn_modules():
+                g, v = m.weight_g, m.weight_v
+                w = nn.Parameter(torch._weight_norm(v.detach(), g.detach(), 0), requires_grad=v.requires_grad)
+                del m._parameters['weight_g'], m._parameters['weight_v']
+                m.__dict__.pop('weight', None)
+                m.register_parameter('weight', w)
+        self.weight_norm, self._wn, self._pack = False, None, None
+        return self
+
+    @staticmethod
+    def remove_weightnorm(model):
+        """glow.py's spelling: ``WaveGlow.remove_weightnorm(model)`` returns the folded model."""
+        return model.remove_weight_norm()
+
+    def _apply(self, fn, recurse=True):
+        super()._apply(fn, recurse)
+        self._pack = None
+        if getattr(self, 'weight_norm', False):
+            self._wn_flatten()                         # .cuda() / .to() gave every parameter an allocation of its own
+        return self
+
+    def _wn_flatten(self):
+        """Lay all ``weight_v`` out in one flat buffer and all ``weight_g`` in another (the parameters become views of
+        them, keeping their identity), beside the buffers of the folded weights and the norms, and build the segment table
+        of csrc/waveglow_wn.hip once.  Tensors start at multiples of 4 floats, so rows of a multiple of 4 floats move
+        as 16-byte accesses."""
+        mods = list(self._wn_modules())
+        dev = mods[0][1].weight_v.device
+        _, glay, _ = self._grad_layout()
+        lay, segs, off, goff = [], [], 0, 0
+        for name, m in mods:
+            shape = tuple(m.weight_v.shape)
+            rows, ln = shape[0], int(np.prod(shape[1:]))
+            lay.append((name, m, off, goff, shape))
+            segs.append((off, goff, glay[name + '.weight'][0], rows, ln))
+            off = -(-(off + rows * ln) // 4) * 4
+            goff += rows
+        host, n_units = nv.wg_weight_norm_table(segs)
+        v = torch.zeros(off, dtype=torch.float32, device=dev)
+        g = torch.zeros(-(-goff // 4) * 4, dtype=torch.float32, device=dev)
+        w, norm = torch.zeros_like(v), torch.zeros_like(g)
+        with torch.no_grad():
+            for name, m, o, go, shape in lay:
+                n = int(np.prod(shape))
+                vv, gg = v[o:o + n].view(shape), g[go:go + shape[0]].view(shape[0], 1, 1)
+                vv.copy_(m.weight_v.detach())
+                gg.copy_(m.weight_g.detach())
+                m.weight_v.data, m.weight_g.data = vv, gg
+                m.weight = w[o:o + n].view(shape)
+        self._wn = dict(dev=dev, v=v, g=g, w=w, norm=norm, host=host, table=host.to(dev), n_units=n_units, lay=lay)
+        self._pack = None
+
+    def _wn_fold(self):
+        """One launch: the folded weights of every weight-normed layer, into the buffer ``module.weight`` is a slice of."""
+        wn = self._wn
+        stale = wn is None or any(m.weight_v.data_ptr() != wn['v'].data_ptr() + 4 * o
+                                  or m.weight_g.data_ptr() != wn['g'].data_ptr() + 4 * go for _, m, o, go, _ in wn['lay'])
+        if stale:                                      # parameters replaced behind the module's back (assign=True, deepcopy)
+            self._wn_flatten()
+            wn = self._wn
+        nv.wg_weight_norm(wn['table'], wn['host'], wn['n_units'], wn['v'], wn['g'], wn['w'], wn['norm'])
+
+    def _wn_grads(self, gout, gv):
+        """One launch: the gradients of every ``weight_g`` / ``weight_v`` from the folded weights' gradients in ``gout``
+        (already times the upstream scalar), added to ``gv`` under the parameters' names."""
+        wn = self._wn
+        nvf, ngf = wn['v'].numel(), wn['g'].numel()
+        buf = torch.empty(nvf + ngf, dtype=torch.float32, device=gout.device)
+        dv, dg = buf[:nvf], buf[nvf:]
+        nv.wg_weight_norm_bwd(wn['table'], wn['host'], wn['n_units'], gout, wn['v'], wn['g'], wn['norm'], dg, dv, 1.0)
+        for name, _, o, go, shape in wn['lay']:
+            gv[name + '.weight_v'] = dv[o:o + int(np.prod(shape))].view(shape)
+            gv[name + '.weight_g'] = dg[go:go + shape[0]].view(shape[0], 1, 1)
 
     # ---- device-side weight layout ------------------------------------------------------------------------------------
     def _packed(self, device):
@@ -223,6 +369,9 @@ class WaveGlow(nn.Module):
         key = (_PACK_GEN[0], str(device), tuple((p.data_ptr(), p._version) for p in self.parameters()))
         if self._pack is not None and self._pack[0] == key:
             return self._pack[1]
+        if self.weight_norm:
+            self._wn_fold()
+            key = (key[0], key[1], tuple((p.data_ptr(), p._version) for p in self.parameters()))
         C, L, G, nm = self.n_channels, self.n_layers, self.n_group, self.n_mel_channels
         taps = UP_KERNEL // HOP
         with torch.no_grad():
@@ -578,9 +727,11 @@ class WaveGlow(nn.Module):
         divided by the number of REAL samples sum_b T_b -- the mean over what was scored, not over the padding.
 
         ``loss.backward()`` gives every parameter of the module that requires grad its float32 gradient, in the
-        parameter's own layout, multiplied by the upstream scalar and added into an existing ``.grad``.  The parameters are
-        the folded weights (``fold_weight_norm``), so these are gradients with respect to the folded weights; training
-        under the g / v weight-norm parametrisation is not supported.  ``spect`` and ``audio`` get no gradient: an input
+        parameter's own layout, multiplied by the upstream scalar and added into an existing ``.grad``.  The parameters of
+        a folded module are the folded weights (``fold_weight_norm``); those of a weight-normed module
+        (``apply_weight_norm``) are glow.py's ``weight_g`` / ``weight_v``: the value is that of the folded module built
+        from ``fold_weight_norm(state_dict())`` and the gradients of all g / v come from one more launch over the folded
+        weights' gradients (csrc/waveglow_wn.hip).  ``spect`` and ``audio`` get no gradient: an input
         that requires grad is refused.  ``precision`` selects the compute of the products in both directions; the
         weights and the gradients are float32 in all three (after ``.half()``: bf16 compute).  Under ``torch.no_grad()``
         (or when no parameter requires grad) the value is the same and nothing is kept.
@@ -625,9 +776,9 @@ class WaveGlow(nn.Module):
                 put('convinv.%d.conv.weight' % j, (n, n, 1))
             calls.append((o0, o - o0))
         o = -(-o // 4) * 4
-        for name, p in self.named_parameters():
+        for name, shape in self._folded_shapes():
             if name not in lay:
-                put(name, p.shape)
+                put(name, shape)
                 o = -(-o // 4) * 4
         return o, lay, calls
 
@@ -733,6 +884,8 @@ class WaveGlow(nn.Module):
         gv['upsample.weight'].view(nm, nm, taps, HOP).copy_(g_up.view(HOP, nm, taps, nm).permute(3, 1, 2, 0))
         nv.colsum(d_cond_g[inner].reshape(-1, nm), ws64, gv['upsample.bias'])
         gout.mul_(upstream.to(device=dev, dtype=torch.float32))
+        if self.weight_norm:
+            self._wn_grads(gout, gv)
         return gv
 
 
@@ -893,8 +1046,9 @@ class Denoiser(nn.Module):
         return self.stft.inverse(audio_spec, audio_angles)
 
 
-def load_waveglow(src, precision='fp32'):
-    """A WaveGlow from a checkpoint path, a state dict, ``{'model': state dict or module}`` or a module."""
+def load_waveglow(src, precision='fp32', weight_norm=False):
+    """A WaveGlow from a checkpoint path, a state dict, ``{'model': state dict or module}`` or a module.
+    ``weight_norm=True`` keeps ``weight_g`` / ``weight_v`` (a module to go on training); the default folds them."""
     if isinstance(src, str):
         src = torch.load(src, map_location='cpu', weights_only=False)
     if isinstance(src, dict) and 'model' in src:
@@ -902,7 +1056,7 @@ def load_waveglow(src, precision='fp32'):
     if isinstance(src, WaveGlow):
         return src
     if isinstance(src, nn.Module):
-        return WaveGlow.from_module(src, precision=precision)
+        return WaveGlow.from_module(src, precision=precision, weight_norm=weight_norm)
     if isinstance(src, dict):
-        return WaveGlow.from_state_dict(src, precision=precision)
+        return WaveGlow.from_state_dict(src, precision=precision, weight_norm=weight_norm)
     raise TypeError("load_waveglow: expected a path, a state dict or a module, got %s" % type(src).__name__)
