@@ -1153,6 +1153,42 @@ int t2amd_hg_post_f32(const float* X, long long x_floats, long long ldx, long lo
 int t2amd_hg_pack_mel_f32(const float* mel, long long mel_floats, int B, int n_mel, long long N, const int* rowb0,
                           const int* rowr0, long long P0, float* out, int ldo, long long out_floats, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Vocos vocoder, inference (csrc/vocos.hip, csrc/vocos_rows.hip; tacotron2_amd/vocos.py).  The arithmetic is restated in
+ * tests/vocos_ref.py.  Everything runs at the frame rate, in the frame-level packed row space of the HiFi-GAN block above
+ * with H0 = 3: [3 | n_0 | 3 | ... | n_{B-1} | 3], rowb0[p] the utterance of packed row p (-1 in a halo), n_rowb >= P.  Every
+ * entry writes all rows of its output and writes zero on rows whose rowb0 is negative; operand rows outside [0, P) read as
+ * zero.  The *_floats arguments are the lengths of the buffers from the pointer on; an entry refuses a buffer shorter than
+ * the rows it addresses.  precision 0 exact f32, 1 split-bf16 x3, 2 bf16.
+ * ------------------------------------------------------------------------------------ */
+/* Depthwise convolution plus LayerNorm over the D channels of every row, one launch:
+ *   y[p][c] = conv_bias[c] + sum_(t < taps) X[p + t - (taps-1)/2][c] w[t D + c]     (taps = 0: y = X, w and conv_bias unused)
+ *   out[p][c] = (y[p][c] - mean_c y[p]) / sqrt(var_c y[p] + eps) ln_w[c] + ln_b[c]  (biased variance)
+ * D a multiple of 32, at most 512; taps 0 or odd, at most 15; all operands 16-byte aligned, ldx and ldout multiples of 4;
+ * out must not be X. */
+int t2amd_vc_dwln_f32(const float* X, long long x_floats, long long ldx, long long P, int D, const float* w,
+                      long long w_floats, const float* conv_bias, int taps, const float* ln_w, const float* ln_b, float eps,
+                      const int* rowb0, long long n_rowb, float* out, long long ldout, long long out_floats, void* stream);
+/* out[m][n] = epi(bias[n] + sum_(k < K) X[m][k] W[n K + k]) for all m < P, n < N.  epi 0: v; 1: exact GELU
+ * v (1 + erf(v / sqrt 2)) / 2; 2: res[m][n] + gamma[n] v (res may be out: each element is read, then written, by the same
+ * lane).  bias may be NULL for epi 0 and 1.  K and N multiples of 32, at most 16416; X and W 16-byte aligned, ldx a multiple
+ * of 4; out must not be X. */
+int t2amd_vc_linear_f32(const float* X, long long x_floats, long long ldx, long long P, int K, const float* W,
+                        long long w_floats, const float* bias, int N, int epi, const float* gamma, const float* res,
+                        long long ldres, long long res_floats, float* out, long long ldout, long long out_floats,
+                        const int* rowb0, long long n_rowb, int precision, void* stream);
+/* Head rows Y[p] = [m_0 .. m_{F-1} | ph_0 .. ph_{F-1}] -> interleaved complex rows:
+ *   S[p][2k, 2k+1] = min(exp(m_k), clamp) (cos ph_k, sin ph_k) for k < F;  zero for F <= k < lds / 2.  lds even. */
+int t2amd_vc_polar_f32(const float* Y, long long y_floats, long long ldy, long long P, int F, float clamp, const int* rowb0,
+                       long long n_rowb, float* S, long long lds, long long s_floats, void* stream);
+/* Overlap-add of windowed inverse-transform frames (L samples a row) into out (B, T).  utt (int32, device) holds
+ * [first packed row, frames n_b] of every utterance.  For t < hop (n_b - 1) + L - 2 trim, with s = t + trim,
+ *   out[b][t] = sum_j frames[row_b + j][s - j hop] / sum_j wsq[s - j hop]   over the frames 0 <= j < n_b that cover s,
+ * in ascending j; out[b][t] = 0 beyond.  wsq[L] is the squared window.  hop divides L, (L - hop) / 2 <= trim <= L / 2
+ * (Vocos' 'same' and 'center' paddings); B at most 65535. */
+int t2amd_vc_ola_f32(const float* frames, long long f_floats, long long ldf, long long P, const float* wsq, const int* utt,
+                     int B, int L, int hop, int trim, float* out, long long T, long long out_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -295,6 +295,7 @@ SYMBOLS = [
     "t2amd_decoder_persist_mailbox_bytes", "t2amd_decoder_persist_supported", "t2amd_decoder_infer_persistent_f32",
     "t2amd_loss_workspace_doubles", "t2amd_tacotron2_loss_fwd_f32", "t2amd_tacotron2_loss_bwd_f32",
     "t2amd_hg_conv_f32", "t2amd_hg_upsample_f32", "t2amd_hg_post_f32", "t2amd_hg_pack_mel_f32",
+    "t2amd_vc_dwln_f32", "t2amd_vc_linear_f32", "t2amd_vc_polar_f32", "t2amd_vc_ola_f32",
 ]
 
 _P, _I, _L, _F, _UL = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_ulonglong
@@ -425,6 +426,10 @@ def _argtypes():
         "t2amd_hg_upsample_f32": [_P, _L, _L, _L, _I, _P, _L, _P, _I, _I, _I, _I, _F, _P, _L, _L, _P, _L, _I, _I, _P],
         "t2amd_hg_post_f32": [_P, _L, _L, _L, _I, _P, _L, _P, _F, _P, _P, _L, _I, _P, _L, _L, _P],
         "t2amd_hg_pack_mel_f32": [_P, _L, _I, _I, _L, _P, _P, _L, _P, _I, _L, _P],
+        "t2amd_vc_dwln_f32": [_P, _L, _L, _L, _I, _P, _L, _P, _I, _P, _P, _F, _P, _L, _P, _L, _L, _P],
+        "t2amd_vc_linear_f32": [_P, _L, _L, _L, _I, _P, _L, _P, _I, _I, _P, _P, _L, _L, _P, _L, _L, _P, _L, _I, _P],
+        "t2amd_vc_polar_f32": [_P, _L, _L, _L, _I, _F, _P, _L, _P, _L, _L, _P],
+        "t2amd_vc_ola_f32": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _I, _P, _L, _L, _P],
     }
 
 
@@ -2140,6 +2145,79 @@ def hg_pack_mel(mel, rowb0, rowr0, out):
     _check(load().t2amd_hg_pack_mel_f32(ptr(_fullc(mel)), _i64(_floats(mel)), B, n_mel, _i64(N), ptr(rowb0, torch.int32),
                                         ptr(rowr0, torch.int32), _i64(P0), po, int(ldo), _i64(_floats(out)), _stream()),
            "t2amd_hg_pack_mel_f32")
+
+
+# ----------------------------------------------------------------------------
+# Vocos vocoder (csrc/vocos.hip, csrc/vocos_rows.hip)
+# ----------------------------------------------------------------------------
+VC_EPI = {None: 0, 'gelu': 1, 'residual': 2}
+
+
+def vc_dwln(X, w, conv_bias, ln_w, ln_b, eps, rowb0, out):
+    """out [P][D] = LayerNorm_D(conv_bias + the depthwise product of the row image X [P][D] with w [taps][D]) * ln_w + ln_b;
+    w None: LayerNorm of X alone.  Zero on rows whose rowb0 is negative."""
+    px, ldx, P, D = _mat(X)
+    po, ldo, Po, Do = _mat(out)
+    taps = 0 if w is None else int(w.shape[0])
+    if (Po, Do) != (P, D) or ln_w.numel() != D or ln_b.numel() != D or \
+            (w is not None and (w.dim() != 2 or w.shape[1] != D or conv_bias is None or conv_bias.numel() != D)):
+        raise NativeError("vc_dwln: shape mismatch X=%s w=%s out=%s" % (tuple(X.shape), None if w is None else tuple(w.shape),
+                                                                        tuple(out.shape)))
+    n_rowb = _hg_map(rowb0)
+    _check(load().t2amd_vc_dwln_f32(px, _i64(_floats(X)), _i64(ldx), _i64(P), D, ptr(_fullc(w)) if w is not None else None,
+                                    _i64(0 if w is None else w.numel()), ptr(_fullc(conv_bias)) if w is not None else None,
+                                    taps, ptr(_fullc(ln_w)), ptr(_fullc(ln_b)), _F(eps), ptr(rowb0, torch.int32), _i64(n_rowb),
+                                    po, _i64(ldo), _i64(_floats(out)), _stream()), "t2amd_vc_dwln_f32")
+
+
+def vc_linear(X, W, bias, epi, gamma, res, out, rowb0, precision):
+    """out [P][N] = epi(bias + X [P][K] W [N][K]^T); epi None, 'gelu' (exact) or 'residual' (res + gamma * .; res may be
+    out).  Zero on rows whose rowb0 is negative."""
+    px, ldx, P, K = _mat(X)
+    pw, ldw, N, Kw = _mat(W)
+    po, ldo, Po, No = _mat(out)
+    if epi not in VC_EPI:
+        raise NativeError("vc_linear: epi must be None, 'gelu' or 'residual', got %r" % (epi,))
+    if Kw != K or ldw != K or Po != P or No != N or (bias is not None and bias.numel() != N) or \
+            (gamma is not None and gamma.numel() != N):
+        raise NativeError("vc_linear: shape mismatch X=%s W=%s out=%s" % (tuple(X.shape), tuple(W.shape), tuple(out.shape)))
+    pr, ldr, nr = None, 0, 0
+    if res is not None:
+        pr, ldr, Pr, Nr = _mat(res)
+        if Pr != P or Nr != N:
+            raise NativeError("vc_linear: res %s beside out %s" % (tuple(res.shape), tuple(out.shape)))
+        nr = _floats(res)
+    n_rowb = _hg_map(rowb0)
+    _check(load().t2amd_vc_linear_f32(px, _i64(_floats(X)), _i64(ldx), _i64(P), K, pw, _i64(_floats(W)),
+                                      ptr(_fullc(bias)) if bias is not None else None, N, VC_EPI[epi],
+                                      ptr(_fullc(gamma)) if gamma is not None else None, pr, _i64(ldr), _i64(nr), po, _i64(ldo),
+                                      _i64(_floats(out)), ptr(rowb0, torch.int32), _i64(n_rowb), int(precision), _stream()),
+           "t2amd_vc_linear_f32")
+
+
+def vc_polar(Y, F, clamp, rowb0, S):
+    """S [P][lds] interleaved (re, im) = min(exp(Y[:, k]), clamp) (cos, sin)(Y[:, F + k]) for k < F, zero pad columns and
+    halo rows."""
+    py, ldy, P, Ny = _mat(Y)
+    ps, lds, Ps, Ns = _mat(S)
+    if Ps != P or Ny < 2 * F or Ns != lds or Ns < 2 * F:
+        raise NativeError("vc_polar: shape mismatch Y=%s S=%s F=%d" % (tuple(Y.shape), tuple(S.shape), F))
+    n_rowb = _hg_map(rowb0)
+    _check(load().t2amd_vc_polar_f32(py, _i64(_floats(Y)), _i64(ldy), _i64(P), int(F), _F(clamp), ptr(rowb0, torch.int32),
+                                     _i64(n_rowb), ps, _i64(lds), _i64(_floats(S)), _stream()), "t2amd_vc_polar_f32")
+
+
+def vc_ola(frames, wsq, utt, hop, trim, out):
+    """out (B, 1, T) = the overlap-add of the frame rows [P][L] of every utterance (utt int32 [B][2]: first row, frames),
+    trimmed by `trim` samples, over the overlap-added squared window wsq [L]; zero beyond each utterance."""
+    pf, ldf, P, L = _mat(frames)
+    if out.dim() != 3 or out.shape[1] != 1 or utt.dtype != torch.int32 or tuple(utt.shape) != (out.shape[0], 2) or \
+            not utt.is_contiguous() or wsq.numel() != L:
+        raise NativeError("vc_ola: shape mismatch frames=%s wsq=%s utt=%s out=%s" % (tuple(frames.shape), tuple(wsq.shape),
+                                                                                      tuple(utt.shape), tuple(out.shape)))
+    _check(load().t2amd_vc_ola_f32(pf, _i64(_floats(frames)), _i64(ldf), _i64(P), ptr(_fullc(wsq)), ptr(utt, torch.int32),
+                                   int(out.shape[0]), int(L), int(hop), int(trim), ptr(_fullc(out)), _i64(out.shape[2]),
+                                   _i64(out.numel()), _stream()), "t2amd_vc_ola_f32")
 
 
 # ----------------------------------------------------------------------------

@@ -1,13 +1,14 @@
-"""mel -> wav with Griffin-Lim, WaveGlow or a HiFi-GAN generator on the GPU.
+"""mel -> wav with Griffin-Lim, WaveGlow, a HiFi-GAN generator or Vocos on the GPU.
 
     python -m tacotron2_amd.vocode MEL.npy [MEL.npy ...] -o DIR [--iters N] [--precision fp32|bf16x3] [--seed S]
     python -m tacotron2_amd.vocode MEL.npy [...] -o DIR --waveglow CKPT [--sigma 0.666] [--denoise STRENGTH]
                                    [--precision fp32|bf16x3|bf16] [--seed S]
     python -m tacotron2_amd.vocode MEL.npy [...] -o DIR --hifigan CKPT [--precision fp32|bf16x3|bf16]
+    python -m tacotron2_amd.vocode MEL.npy [...] -o DIR --vocos CKPT [--precision fp32|bf16x3|bf16]
 
 Reads (n_mel, n) float32 log-mels (what ``precompute_mels`` writes) or (B, n_mel, n) batches (one wav per item,
 ``<stem>_<b>.wav``), vocodes them as one ragged batch (``TacotronSTFT.vocode``, or ``WaveGlow.infer`` and optionally
-``Denoiser`` with ``--waveglow``, or ``hifigan.Generator.infer`` with ``--hifigan``: 256 samples per mel frame) and writes ``DIR/<stem>.wav``: 16-bit PCM at
+``Denoiser`` with ``--waveglow``, or ``hifigan.Generator.infer`` with ``--hifigan``, or ``vocos.Vocos.infer`` with ``--vocos``: 256 samples per mel frame) and writes ``DIR/<stem>.wav``: 16-bit PCM at
 ``hparams.sampling_rate``, the signal clipped to [-1, 1] and scaled by ``max_wav_value``.
 """
 import argparse
@@ -24,12 +25,14 @@ def main(argv=None):
     ap.add_argument("-o", "--out-dir", required=True)
     ap.add_argument("--iters", type=int, default=30, help="Griffin-Lim iterations (default 30)")
     ap.add_argument("--precision", choices=("fp32", "bf16x3", "bf16"), default="fp32",
-                    help="bf16 applies to WaveGlow and HiFi-GAN only")
+                    help="bf16 applies to WaveGlow, HiFi-GAN and Vocos only")
     ap.add_argument("--seed", type=int, default=None,
                     help="np.random.seed before the initial angles are drawn (torch.manual_seed with --waveglow)")
     ap.add_argument("--waveglow", default=None, metavar="CKPT", help="vocode with this WaveGlow checkpoint")
     ap.add_argument("--hifigan", default=None, metavar="CKPT",
                     help="vocode with this HiFi-GAN generator checkpoint ({'generator': state dict}, weight-normed or folded)")
+    ap.add_argument("--vocos", default=None, metavar="CKPT",
+                    help="vocode with this Vocos checkpoint (a state dict or {'state_dict': ...}; hop from hparams, padding 'same')")
     ap.add_argument("--sigma", type=float, default=None, help="WaveGlow noise scale (default 0.666)")
     ap.add_argument("--denoise", type=float, default=0.0, metavar="STRENGTH",
                     help="WaveGlow Denoiser strength (default 0 = off)")
@@ -43,6 +46,13 @@ def main(argv=None):
             ap.error("--sigma is WaveGlow's noise scale: a HiFi-GAN generator draws no noise")
         if args.denoise > 0:
             ap.error("--denoise is WaveGlow's Denoiser (built from a WaveGlow's bias response): not available with --hifigan")
+    if args.vocos:
+        if args.waveglow or args.hifigan:
+            ap.error("--vocos, --hifigan and --waveglow are three vocoders: give one")
+        if args.sigma is not None:
+            ap.error("--sigma is WaveGlow's noise scale: Vocos draws no noise")
+        if args.denoise > 0:
+            ap.error("--denoise is WaveGlow's Denoiser (built from a WaveGlow's bias response): not available with --vocos")
     sigma = 0.666 if args.sigma is None else args.sigma
     from .audio import TacotronSTFT
     from .hparams import create_hparams
@@ -83,6 +93,18 @@ def main(argv=None):
                              % (args.hifigan, hg.n_mel_channels, hp.n_mel_channels))
         wav = hg.infer(torch.from_numpy(batch).cuda(), lengths=lengths)[:, 0].float().cpu().numpy()
         n_samples = [hg.hop * n for n in lengths]
+    elif args.vocos:
+        from .vocos import load_vocos
+        try:
+            vc = load_vocos(args.vocos, precision=args.precision, hop_length=hp.hop_length)
+        except ValueError as e:
+            raise SystemExit("%s: with hop %d from hparams: %s" % (args.vocos, hp.hop_length, e))
+        if vc.n_mel_channels != hp.n_mel_channels:
+            raise SystemExit("%s: the model takes %d mel channels, the mels have %d"
+                             % (args.vocos, vc.n_mel_channels, hp.n_mel_channels))
+        vc = vc.cuda().eval()
+        wav = vc.infer(torch.from_numpy(batch).cuda(), lengths=lengths)[:, 0].float().cpu().numpy()
+        n_samples = [vc.samples(n) for n in lengths]
     else:
         stft = TacotronSTFT(hp.filter_length, hp.hop_length, hp.win_length, hp.n_mel_channels, hp.sampling_rate,
                             hp.mel_fmin, hp.mel_fmax)

@@ -1,0 +1,377 @@
+"""Vocos vocoder (Siuzdak 2023) on the MI355X: mel -> waveform at the frame rate, inference only.
+
+    vc = load_vocos("vocos_mel_22khz.pt").cuda().eval()   # a state dict, {'state_dict': ...} or a module
+    audio = vc(mel)                                         # (B, 80, N) log-mels -> (B, 1, 256 N) float32
+    audio = vc.infer(mel, lengths=frames)                   # ragged: every utterance as if alone, zero beyond hop n_b
+
+A ConvNeXt stack on D-channel frame rows, one linear head that predicts log-magnitude and phase, one inverse STFT: nothing
+runs at the sample rate before the overlap-add.  The module keeps the published names (``backbone.embed``, ``backbone.norm``,
+``backbone.convnext.{i}.dwconv`` / ``.norm`` / ``.pwconv1`` / ``.pwconv2`` / ``.gamma``, ``backbone.final_layer_norm``,
+``head.out``, ``head.istft.window``); ``feature_extractor.*`` keys of a published checkpoint are ignored (the mel front end is
+this project's), a checkpoint with an ``adanorm`` backbone (EnCodec features) is refused.  The geometry is read from the
+tensor shapes; hop and padding are not in the shapes: they default to n_fft / 4 and 'same'.  Weights are f32 masters;
+``precision`` selects the compute of the two products of every block: 'fp32' (exact f32 MFMA), 'bf16x3' or 'bf16'.  The head
+product and the inverse DFT stay at f32 or split-bf16 even with 'bf16': phase error goes straight into the waveform.
+``.half()`` keeps the f32 weights, selects 'bf16' and returns float16.
+
+Per call: mel packing, embed, LayerNorm; per block three launches (dwconv + LayerNorm, pwconv1 + GELU, pwconv2 with gamma and
+the residual); LayerNorm, head, polar, inverse DFT, overlap-add.  One workspace allocation per call; the layer loop does no
+allocation, copy or host synchronisation and has no loop over utterances.  The arithmetic is restated in float64 torch by
+tests/vocos_ref.py; DESIGN.md section 12 has the layout.
+"""
+import numpy as np
+import torch
+from torch import nn
+
+from . import native as nv
+from .hifigan import _ce, pack_conv
+from .waveglow import PRECISIONS
+
+EMBED_KERNEL = DW_KERNEL = 7
+LN_EPS = 1e-6
+MAG_CLAMP = 100.0
+HALO = 3                          # zero rows around every utterance: the 7-tap windows, and (n_fft - hop) / hop frames of tail
+MAX_ROWS = 2 ** 31 - 256          # csrc/vocos.hip VC_MAX_ROWS
+MAX_DIM = 512
+MAX_INTERMEDIATE = 2048
+MAX_N_FFT = 16384
+PADDINGS = ('same', 'center')
+
+
+def _pad_cols(n):
+    """Columns of the head product: a multiple of 32, and of 128 (the widest tile) once there is more than one such tile."""
+    return -(-n // 32) * 32 if n <= 128 else -(-n // 128) * 128
+
+
+def config_from_state_dict(state_dict, hop_length=None, padding='same'):
+    """Vocos constructor arguments from the tensor shapes of a state dict."""
+    sd = state_dict
+    bad = sorted(k for k in sd if 'adanorm' in k or k.endswith('.norm.scale.weight') or k.endswith('.norm.shift.weight'))
+    if bad:
+        raise ValueError("Vocos: the checkpoint has an adanorm backbone (%s ...): EnCodec-feature models are not covered, only "
+                         "the mel models with LayerNorm" % bad[0])
+    for k in ('backbone.embed.weight', 'backbone.convnext.0.pwconv1.weight', 'head.out.weight'):
+        if k not in sd:
+            raise ValueError("Vocos: missing %s: not a Vocos state dict" % k)
+    layers = sorted({int(k.split('.')[2]) for k in sd if k.startswith('backbone.convnext.')})
+    if layers != list(range(len(layers))):
+        raise ValueError("Vocos: backbone.convnext layers %s are not 0 .. L-1" % layers)
+    emb = sd['backbone.embed.weight']
+    two_f = int(sd['head.out.weight'].shape[0])
+    n_fft = two_f - 2
+    if emb.dim() != 3 or emb.shape[2] != EMBED_KERNEL or two_f < 4 or two_f % 2:
+        raise ValueError("Vocos: embed %s / head.out %s are not Conv1d(n_mel, D, 7) and Linear(D, n_fft + 2)"
+                         % (tuple(emb.shape), tuple(sd['head.out.weight'].shape)))
+    if 'head.istft.window' in sd and sd['head.istft.window'].numel() != n_fft:
+        raise ValueError("Vocos: head.istft.window has %d samples, head.out predicts n_fft = %d"
+                         % (sd['head.istft.window'].numel(), n_fft))
+    return dict(n_mel_channels=int(emb.shape[1]), dim=int(emb.shape[0]),
+                intermediate_dim=int(sd['backbone.convnext.0.pwconv1.weight'].shape[0]), num_layers=len(layers), n_fft=n_fft,
+                hop_length=int(hop_length) if hop_length is not None else n_fft // 4, padding=padding)
+
+
+class ConvNeXtBlock(nn.Module):
+    def __init__(self, dim, intermediate_dim):
+        super().__init__()
+        self.dwconv = nn.Conv1d(dim, dim, DW_KERNEL, padding=DW_KERNEL // 2, groups=dim)
+        self.norm = nn.LayerNorm(dim, eps=LN_EPS)
+        self.pwconv1 = nn.Linear(dim, intermediate_dim)
+        self.pwconv2 = nn.Linear(intermediate_dim, dim)
+        self.gamma = nn.Parameter(torch.full((dim,), 1.0 / 8))
+
+
+class Backbone(nn.Module):
+    def __init__(self, n_mel_channels, dim, intermediate_dim, num_layers):
+        super().__init__()
+        self.embed = nn.Conv1d(n_mel_channels, dim, EMBED_KERNEL, padding=EMBED_KERNEL // 2)
+        self.norm = nn.LayerNorm(dim, eps=LN_EPS)
+        self.convnext = nn.ModuleList([ConvNeXtBlock(dim, intermediate_dim) for _ in range(num_layers)])
+        self.final_layer_norm = nn.LayerNorm(dim, eps=LN_EPS)
+
+
+class ISTFT(nn.Module):
+    def __init__(self, n_fft):
+        super().__init__()
+        self.register_buffer('window', torch.hann_window(n_fft, periodic=True))
+
+
+class Head(nn.Module):
+    def __init__(self, dim, n_fft):
+        super().__init__()
+        self.out = nn.Linear(dim, n_fft + 2)
+        self.istft = ISTFT(n_fft)
+
+
+def inverse_basis(window):
+    """[n_fft][ceil32(n_fft + 2)] float32: frame[t] = sum_k S[2k] basis[t][2k] + S[2k+1] basis[t][2k+1] is
+    window[t] irfft(S, n_fft)[t] for interleaved (re, im) rows S; built in float64 with exact angle reduction."""
+    w = window.detach().double().cpu()
+    L = w.numel()
+    F = L // 2 + 1
+    t = torch.arange(L, dtype=torch.int64)[:, None]
+    k = torch.arange(F, dtype=torch.int64)[None, :]
+    ang = ((t * k) % L).double() * (2.0 * np.pi / L)
+    c = torch.full((F,), 2.0, dtype=torch.float64)
+    c[0] = c[-1] = 1.0
+    out = torch.zeros(L, -(-2 * F // 32) * 32, dtype=torch.float64)
+    out[:, 0:2 * F:2] = torch.cos(ang) * c * (w[:, None] / L)
+    out[:, 1:2 * F:2] = -torch.sin(ang) * c * (w[:, None] / L)
+    out[:, 1] = 0.0                       # irfft ignores the imaginary parts of DC and Nyquist
+    out[:, 2 * F - 1] = 0.0
+    return out.float()
+
+
+class Vocos(nn.Module):
+    def __init__(self, n_mel_channels=80, dim=512, intermediate_dim=1536, num_layers=8, n_fft=1024, hop_length=256,
+                 padding='same', precision='fp32'):
+        super().__init__()
+        D, I, L, hop = int(dim), int(intermediate_dim), int(n_fft), int(hop_length)
+        if D < 32 or D % 32 or D > MAX_DIM:
+            raise ValueError("Vocos: dim %d is not covered by the kernels (a multiple of 32 up to %d)" % (D, MAX_DIM))
+        if I < 32 or I % 32 or I > MAX_INTERMEDIATE:
+            raise ValueError("Vocos: intermediate_dim %d is not covered by the kernels (a multiple of 32 up to %d)"
+                             % (I, MAX_INTERMEDIATE))
+        if num_layers < 1:
+            raise ValueError("Vocos: num_layers must be at least 1, got %d" % num_layers)
+        if n_mel_channels < 1 or _ce(n_mel_channels) > MAX_DIM:
+            raise ValueError("Vocos: n_mel_channels must be 1 to %d, got %d" % (MAX_DIM, n_mel_channels))
+        if L < 32 or L % 32 or L > MAX_N_FFT:
+            raise ValueError("Vocos: n_fft %d is not covered by the kernels (a multiple of 32 up to %d)" % (L, MAX_N_FFT))
+        if hop < 1 or L % hop:
+            raise ValueError("Vocos: hop %d does not divide n_fft %d (the overlap-added window must be periodic in hop)" % (hop, L))
+        if (L - hop) % 2:
+            raise ValueError("Vocos: n_fft %d - hop %d is odd; the 'same' trim (n_fft - hop) / 2 is whole for an even "
+                             "difference only" % (L, hop))
+        if 2 * hop > L or L // hop - 1 > HALO:
+            raise ValueError("Vocos: hop %d with n_fft %d: 2 to %d frames must overlap (the %d halo rows hold an utterance's "
+                             "tail)" % (hop, L, HALO + 1, HALO))
+        if padding not in PADDINGS:
+            raise ValueError("Vocos: padding must be 'same' or 'center', got %r" % (padding,))
+        self.n_mel_channels, self.dim, self.intermediate_dim, self.num_layers = int(n_mel_channels), D, I, int(num_layers)
+        self.n_fft, self.hop, self.padding = L, hop, padding
+        self.backbone = Backbone(self.n_mel_channels, D, I, self.num_layers)
+        self.head = Head(D, L)
+        self.precision = precision
+        self.half_io = False
+        self._pack = None
+        self._plan_cache = None
+
+    hop_length = property(lambda self: self.hop)
+
+    def config(self):
+        return dict(n_mel_channels=self.n_mel_channels, dim=self.dim, intermediate_dim=self.intermediate_dim,
+                    num_layers=self.num_layers, n_fft=self.n_fft, hop_length=self.hop, padding=self.padding)
+
+    # ---- precision / dtype -------------------------------------------------------------------------------------------
+    @property
+    def precision(self):
+        return self._precision
+
+    @precision.setter
+    def precision(self, p):
+        if p not in PRECISIONS:
+            raise ValueError("Vocos: precision must be one of %s, got %r" % (sorted(PRECISIONS), p))
+        self._precision = p
+
+    def half(self):
+        """f32 master weights kept; bf16 compute in the blocks, float16 output."""
+        self.precision, self.half_io = 'bf16', True
+        return self
+
+    def float(self):
+        super().float()
+        self.precision, self.half_io = 'fp32', False
+        return self
+
+    def _apply(self, fn, recurse=True):
+        super()._apply(fn, recurse)
+        self._pack = self._plan_cache = None
+        return self
+
+    # ---- loading ------------------------------------------------------------------------------------------------------
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        """Takes a Vocos state dict; ``feature_extractor.*`` keys (the published mel front end) are dropped."""
+        sd = {k: v for k, v in state_dict.items() if not k.startswith('feature_extractor.')}
+        cfg = config_from_state_dict(sd, hop_length=self.hop, padding=self.padding)
+        if cfg != self.config():
+            raise ValueError("Vocos: state dict geometry %s does not match the module's %s" % (cfg, self.config()))
+        sd = {k: v.float() if torch.is_tensor(v) and v.is_floating_point() else v for k, v in sd.items()}
+        self._pack = None
+        return super().load_state_dict(sd, strict=strict, assign=assign)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, precision='fp32', hop_length=None, padding='same'):
+        sd = {k: v for k, v in state_dict.items() if not k.startswith('feature_extractor.')}
+        m = cls(precision=precision, **config_from_state_dict(sd, hop_length, padding))
+        m.load_state_dict(sd)
+        return m
+
+    @classmethod
+    def from_module(cls, module, precision='fp32', hop_length=None, padding='same'):
+        """Adopt a loaded reference model: its weights are read once."""
+        with torch.no_grad():
+            sd = {k: v.detach().float().cpu() for k, v in module.state_dict().items()}
+        return cls.from_state_dict(sd, precision, hop_length, padding)
+
+    # ---- row plan -----------------------------------------------------------------------------------------------------
+    def trim(self):
+        """Samples cut from each end of an utterance's overlap-add."""
+        return (self.n_fft - self.hop) // 2 if self.padding == 'same' else self.n_fft // 2
+
+    def samples(self, n):
+        """Samples of an utterance of n frames."""
+        return self.hop * n if self.padding == 'same' else self.hop * (n - 1)
+
+    def row_windows(self):
+        """[(lowest row offset, highest row offset)] of every launch that reads other rows than its own: embed, every dwconv,
+        and the overlap-add (the rows whose frames reach the samples of row r's hop, either padding)."""
+        reach = self.n_fft // self.hop - 1
+        return [(-(EMBED_KERNEL // 2), EMBED_KERNEL // 2)] + [(-(DW_KERNEL // 2), DW_KERNEL // 2)] * self.num_layers + \
+            [(-reach, reach)]
+
+    def packed_plan(self, lengths):
+        """(rowb0, rowr0, utt, offsets, P) of the packed row space for per-utterance frame counts (host tensors)."""
+        H = HALO
+        rowb, rowr, offs = [np.full(H, -1, np.int32)], [np.zeros(H, np.int32)], []
+        pos = H
+        for b, n in enumerate(lengths):
+            n = int(n)
+            offs.append(pos)
+            rowb += [np.full(n, b, np.int32), np.full(H, -1, np.int32)]
+            rowr += [np.arange(n, dtype=np.int32), np.zeros(H, np.int32)]
+            pos += n + H
+        utt = torch.tensor([[o, int(n)] for o, n in zip(offs, lengths)], dtype=torch.int32)
+        return torch.from_numpy(np.concatenate(rowb)), torch.from_numpy(np.concatenate(rowr)), utt, offs, pos
+
+    def row_widths(self):
+        """Floats per packed row of the workspace regions: mels, two D-wide images, the intermediate, head, spectrum, frames."""
+        two_f = self.n_fft + 2
+        return [_ce(self.n_mel_channels), self.dim, self.dim, self.intermediate_dim, _pad_cols(two_f), -(-two_f // 32) * 32,
+                self.n_fft]
+
+    def workspace_floats(self, P):
+        return P * sum(self.row_widths())
+
+    def _plan(self, lens, dev):
+        key = (tuple(lens), str(dev))
+        if self._plan_cache is not None and self._plan_cache[0] == key:
+            return self._plan_cache[1]
+        rowb0, rowr0, utt, offs, P = self.packed_plan(lens)
+        if P > MAX_ROWS:
+            raise ValueError("Vocos: %d packed frames exceed the %d rows one call can address; split the batch" % (P, MAX_ROWS))
+        plan = (rowb0.to(dev), rowr0.to(dev), utt.to(dev), P)
+        self._plan_cache = (key, plan)
+        return plan
+
+    # ---- device-side weight layout ------------------------------------------------------------------------------------
+    def _packed(self, device):
+        tensors = list(self.parameters()) + list(self.buffers())
+        key = (str(device), tuple((p.data_ptr(), p._version) for p in tensors))
+        if self._pack is not None and self._pack[0] == key:
+            return self._pack[1]
+
+        def f(t):
+            return t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+        with torch.no_grad():
+            bb, two_f = self.backbone, self.n_fft + 2
+            pk = dict(embed=pack_conv(bb.embed.weight.detach().to(device), bb.embed.bias.detach().to(device),
+                                      _ce(self.n_mel_channels), self.dim),
+                      norm=(f(bb.norm.weight), f(bb.norm.bias)), final=(f(bb.final_layer_norm.weight), f(bb.final_layer_norm.bias)),
+                      blocks=[])
+            for blk in bb.convnext:
+                pk['blocks'].append(dict(dw=(f(blk.dwconv.weight[:, 0, :].t()), f(blk.dwconv.bias)),
+                                         norm=(f(blk.norm.weight), f(blk.norm.bias)),
+                                         pw1=(f(blk.pwconv1.weight), f(blk.pwconv1.bias)),
+                                         pw2=(f(blk.pwconv2.weight), f(blk.pwconv2.bias)), gamma=f(blk.gamma)))
+            nh = _pad_cols(two_f)
+            hw = torch.zeros(nh, self.dim, dtype=torch.float32, device=device)
+            hb = torch.zeros(nh, dtype=torch.float32, device=device)
+            hw[:two_f], hb[:two_f] = f(self.head.out.weight), f(self.head.out.bias)
+            pk['head'] = (hw, hb)
+            win = self.head.istft.window
+            pk['basis'] = inverse_basis(win).to(device)
+            pk['wsq'] = (win.detach().double().cpu() ** 2).float().to(device)
+        self._pack = (key, pk)
+        return pk
+
+    # ---- inference ----------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def infer(self, mel, lengths=None):
+        """(B, n_mel, N) log-mels (float32 / float16 / bfloat16) -> (B, 1, hop N) audio ('center': hop (N - 1); float16 after
+        ``.half()``).  ``lengths``: frames per utterance (ragged: each computed as if alone, zero beyond its samples)."""
+        dev = self.head.out.weight.device
+        if dev.type != 'cuda' and not nv.validate_only():
+            raise nv.NativeError("Vocos: move the module to the MI355X first (.cuda()); there is no CPU path")
+        if not torch.is_tensor(mel) or mel.dim() != 3 or mel.shape[1] != self.n_mel_channels:
+            raise ValueError("Vocos.infer: expected (B, %d, N) mels, got %s"
+                             % (self.n_mel_channels, tuple(mel.shape) if torch.is_tensor(mel) else type(mel)))
+        if mel.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError("Vocos.infer: mels must be float32, float16 or bfloat16, got %s" % mel.dtype)
+        B, nm, N = mel.shape
+        lens = [N] * B if lengths is None else [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if B < 1 or N < 1 or len(lens) != B or min(lens) < 1 or max(lens) > N:
+            raise ValueError("Vocos.infer: lengths %s do not fit %d utterances of %d frames" % (lens, B, N))
+        T = self.samples(N)
+        if T < 1 or B > 65535:
+            raise ValueError("Vocos.infer: %d utterances of %d frames give %d samples with padding %r (1 to 65535 utterances, "
+                             "at least one sample)" % (B, N, T, self.padding))
+        prec = PRECISIONS[self.precision]
+        head_prec = min(prec, 1)
+        rowb0, rowr0, utt, P = self._plan(lens, dev)
+        total = self.workspace_floats(P)
+        if dev.type == 'cuda':
+            free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+            if 4 * (total + B * T) > free:
+                raise nv.NativeError("Vocos.infer: the workspace needs %.2f GB (%d packed frames) and %.2f GB are free; "
+                                     "split the batch" % (4 * total / 1e9, P, free / 1e9))
+        pk = self._packed(dev)
+        x32 = mel.to(device=dev, dtype=torch.float32).contiguous()
+        ws = torch.empty(total, dtype=torch.float32, device=dev)
+        out = torch.empty(B, 1, T, dtype=torch.float32, device=dev)
+        regions, pos = [], 0
+        for wdt in self.row_widths():
+            regions.append(ws[pos:pos + P * wdt].view(P, wdt))
+            pos += P * wdt
+        mel_cl, x, t, h, y, spec, frames = regions
+        nv.hg_pack_mel(x32, rowb0, rowr0, mel_cl)
+        nv.hg_conv(mel_cl, pk['embed'][0], pk['embed'][1], EMBED_KERNEL, 1, None, None, t, 1.0, False, rowb0, 1, prec)
+        nv.vc_dwln(t, None, None, pk['norm'][0], pk['norm'][1], LN_EPS, rowb0, x)
+        for blk in pk['blocks']:
+            nv.vc_dwln(x, blk['dw'][0], blk['dw'][1], blk['norm'][0], blk['norm'][1], LN_EPS, rowb0, t)
+            nv.vc_linear(t, blk['pw1'][0], blk['pw1'][1], 'gelu', None, None, h, rowb0, prec)
+            nv.vc_linear(h, blk['pw2'][0], blk['pw2'][1], 'residual', blk['gamma'], x, x, rowb0, prec)
+        nv.vc_dwln(x, None, None, pk['final'][0], pk['final'][1], LN_EPS, rowb0, t)
+        nv.vc_linear(t, pk['head'][0], pk['head'][1], None, None, None, y, rowb0, head_prec)
+        nv.vc_polar(y, self.n_fft // 2 + 1, MAG_CLAMP, rowb0, spec)
+        nv.vc_linear(spec, pk['basis'], None, None, None, None, frames, rowb0, head_prec)
+        nv.vc_ola(frames, pk['wsq'], utt, self.hop, self.trim(), out)
+        return out.half() if self.half_io else out
+
+    def forward(self, mel):
+        """The reference's ``decode`` of mel features."""
+        return self.infer(mel)
+
+
+def load_vocos(src, precision=None, hop_length=None, padding=None):
+    """A Vocos from a checkpoint path, a state dict, ``{'state_dict': state dict}`` or a module.  ``precision`` defaults to
+    'fp32', ``hop_length`` to n_fft / 4, ``padding`` to 'same'.  A Vocos instance is returned as it is, with ``precision``
+    set when given; a hop or padding other than its own is refused (they are part of its geometry)."""
+    if isinstance(src, str):
+        src = torch.load(src, map_location='cpu', weights_only=False)
+    if isinstance(src, dict) and 'state_dict' in src and not torch.is_tensor(src['state_dict']):
+        src = src['state_dict']
+    if isinstance(src, Vocos):
+        if (hop_length is not None and int(hop_length) != src.hop) or (padding is not None and padding != src.padding):
+            raise ValueError("load_vocos: the module has hop %d and padding %r, asked for hop %s and padding %r"
+                             % (src.hop, src.padding, hop_length, padding))
+        if precision is not None:
+            src.precision = precision
+        return src
+    precision = 'fp32' if precision is None else precision
+    padding = 'same' if padding is None else padding
+    if isinstance(src, nn.Module):
+        return Vocos.from_module(src, precision=precision, hop_length=hop_length, padding=padding)
+    if isinstance(src, dict):
+        return Vocos.from_state_dict(src, precision=precision, hop_length=hop_length, padding=padding)
+    raise TypeError("load_vocos: expected a path, a state dict or a module, got %s" % type(src).__name__)
