@@ -195,3 +195,6 @@ int t2amd_check_lstm_bwd_(const t2amd_lstm_bwd* a);      // rnn.hip: argument ch
 
 static inline bool t2_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int t2_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// The most rows of a packed row image (HiFi-GAN, Vocos): 2^31 - 256, so that grid.x = rows / 128 and 32-bit row sums hold
+#define T2_MAX_ROWS 2147483392LL

@@ -17,7 +17,11 @@
 // multi-receptive-field sum (first block stores, later blocks add, one launch after the other: no atomics).
 // Precision 0 exact f32 (v_mfma_f32_32x32x2_f32), 1 split-bf16 x 3, 2 bf16 (v_mfma_f32_32x32x16_bf16).
 // The two element-wise ends of the path (mel packing, conv_post) are in hifigan_post.hip.
-#include "common.h"
+//
+// The tile loop itself (LDS images, K loop, MFMA nest, once per precision family) is csrc/rowmma.h, shared with
+// waveglow_layer.hip and vocos.hip.  This file owns the parameters, how a row of A is fetched (HgRows: bounds test,
+// leaky-ReLU, the phase's taps), the epilogue, the __global__ wrappers with their grid mapping, and the C entries.
+#include "rowmma.h"
 
 struct HgConvParams {
     const float* X;
@@ -93,242 +97,49 @@ __device__ __forceinline__ void hg_taps(const HgConvParams& p, int phase, int& b
     }
 }
 
-// ---- exact f32: 128 x BN x 16 tiles, both operands transposed into k-major LDS -----------------------------------------
-#define HBK 16
+// The rows of one 128 x BN tile for csrc/rowmma.h: 64-bit rows, every shifted row tested against [0, P), leaky-ReLU on the
+// operand while it is loaded, the tap of a K-step taken once per step.  Build it in place in the kernel: returned by value
+// from a helper, the reference it holds keeps the compiler from reading the kernel arguments once at entry, and the epilogue
+// then re-reads them from memory row by row.
+struct HgRows {
+    const HgConvParams& p;
+    long long row0;
+    int col0, phase, tbase, tstep;
+    __device__ __forceinline__ HgRows(const HgConvParams& p_, long long row0_, int col0_, int phase_)
+        : p(p_), row0(row0_), col0(col0_), phase(phase_) {
+        hg_taps(p, phase, tbase, tstep);
+    }
+    __device__ __forceinline__ RmStep step(int k0) const {
+        const int tap = k0 / p.Cin;
+        return {tbase + tap * tstep, k0 - tap * p.Cin};
+    }
+    __device__ __forceinline__ float4 a(const RmStep& s, int r, int kc) const {
+        const long long src = row0 + r + s.off;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row0 + r < p.P && src >= 0 && src < p.P) {
+            v = *reinterpret_cast<const float4*>(p.X + src * p.ldx + s.col + kc);
+            if (p.act) v = hg_lrelu4(v, p.slope);
+        }
+        return v;
+    }
+    template <int TM, int TN>
+    __device__ __forceinline__ void epilogue(f32x16 (&acc)[TM][TN], int wm, int wn, int lane) const {
+        hg_conv_epilogue<TM, TN>(p, acc, row0, col0, wm, wn, lane, phase);
+    }
+};
 
+// blockIdx.x = row tile, blockIdx.y = column tile, blockIdx.z = phase (W[phase] the weight slice of a transposed convolution)
 template <int WMW, int WNW, int TM, int TN>
 __global__ __launch_bounds__(256) void hg_conv_f32_kernel(HgConvParams p) {
-    constexpr int BM = WMW * TM * 32, BN = WNW * TN * 32;
-    static_assert(BM == 128 && WMW * WNW == 4, "4 waves over 128 rows");
-    constexpr int B_IT = (BN * 4 + 255) / 256;
-    __shared__ __attribute__((aligned(16))) float As[2][HBK][BM + 4];
-    __shared__ __attribute__((aligned(16))) float Bs[2][HBK][BN + 4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WNW, wn = wave % WNW;
-    const long long row0 = (long long)blockIdx.x * BM;
-    const int col0 = blockIdx.y * BN;
-    const int phase = blockIdx.z;
-    const float* W = p.W + (long long)phase * p.N * p.K;
-    int tbase, tstep;
-    hg_taps(p, phase, tbase, tstep);
-    const int nk = p.K / HBK;
-    float4 ra[2], rb[B_IT];
-
-    auto load = [&](int k0) {
-        const int tap = k0 / p.Cin;
-        const int off = tbase + tap * tstep;
-        const int col = k0 - tap * p.Cin;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = tid + 256 * i;
-            const int r = f >> 2, kq = f & 3;
-            const long long src = row0 + r + off;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row0 + r < p.P && src >= 0 && src < p.P) {
-                v = *reinterpret_cast<const float4*>(p.X + src * p.ldx + col + kq * 4);
-                if (p.act) v = hg_lrelu4(v, p.slope);
-            }
-            ra[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < B_IT; ++i) {
-            const int f = tid + 256 * i;
-            const int r = f >> 2, kq = f & 3;
-            const int gn = col0 + r;
-            rb[i] = (f < BN * 4 && gn < p.N) ? *reinterpret_cast<const float4*>(W + (long long)gn * p.K + k0 + kq * 4)
-                                             : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = tid + 256 * i;
-            const int r = f >> 2, kq = f & 3;
-            As[buf][kq * 4 + 0][r] = ra[i].x;
-            As[buf][kq * 4 + 1][r] = ra[i].y;
-            As[buf][kq * 4 + 2][r] = ra[i].z;
-            As[buf][kq * 4 + 3][r] = ra[i].w;
-        }
-#pragma unroll
-        for (int i = 0; i < B_IT; ++i) {
-            const int f = tid + 256 * i;
-            const int r = f >> 2, kq = f & 3;
-            if (f < BN * 4) {
-                Bs[buf][kq * 4 + 0][r] = rb[i].x;
-                Bs[buf][kq * 4 + 1][r] = rb[i].y;
-                Bs[buf][kq * 4 + 2][r] = rb[i].z;
-                Bs[buf][kq * 4 + 3][r] = rb[i].w;
-            }
-        }
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    load(0);
-    store(0);
-    __syncthreads();
-    const int l31 = lane & 31, lhi = lane >> 5;
-    int cur = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        const bool more = kt + 1 < nk;
-        if (more) load((kt + 1) * HBK);
-#pragma unroll
-        for (int kk = 0; kk < HBK / 2; ++kk) {
-            const int krow = kk * 2 + lhi;
-            float a[TM], b[TN];
-#pragma unroll
-            for (int t = 0; t < TM; ++t) a[t] = As[cur][krow][(wm * TM + t) * 32 + l31];
-#pragma unroll
-            for (int t = 0; t < TN; ++t) b[t] = Bs[cur][krow][(wn * TN + t) * 32 + l31];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-        if (more) store(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
-    }
-    hg_conv_epilogue<TM, TN>(p, acc, row0, col0, wm, wn, lane, phase);
+    const HgRows rows(p, (long long)blockIdx.x * 128, blockIdx.y * (WNW * TN * 32), blockIdx.z);
+    rm_tile_f32<WMW, WNW, TM, TN>(rows, p.W + (long long)rows.phase * p.N * p.K, p.N, p.K, rows.col0);
 }
-
-// ---- split-bf16 x 3 (X3) / plain bf16: 128 x BN x 32 tiles, K-contiguous bf16 LDS rows (stride 40) --------------------
-typedef short hg_bf16x8 __attribute__((ext_vector_type(8)));
-#define HHK 32
-#define HHLD 40
 
 template <bool X3, int WMW, int WNW, int TM, int TN>
 __global__ __launch_bounds__(256) void hg_conv_bf16_kernel(HgConvParams p) {
-    constexpr int NH = X3 ? 2 : 1;
-    constexpr int BM = WMW * TM * 32, BN = WNW * TN * 32;
-    static_assert(BM == 128 && WMW * WNW == 4, "4 waves over 128 rows");
-    constexpr int B_IT = BN * 8 / 256;
-    constexpr int IMGA = BM * HHLD, IMGB = BN * HHLD;
-    __shared__ __attribute__((aligned(16))) unsigned short As[2][NH * IMGA];
-    __shared__ __attribute__((aligned(16))) unsigned short Bs[2][NH * IMGB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WNW, wn = wave % WNW;
-    const long long row0 = (long long)blockIdx.x * BM;
-    const int col0 = blockIdx.y * BN;
-    const int phase = blockIdx.z;
-    const float* W = p.W + (long long)phase * p.N * p.K;
-    int tbase, tstep;
-    hg_taps(p, phase, tbase, tstep);
-    const int nk = p.K / HHK;
-    float4 ra[4], rb[B_IT];
-
-    auto load = [&](int k0) {
-        const int tap = k0 / p.Cin;
-        const int off = tbase + tap * tstep;
-        const int col = k0 - tap * p.Cin;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int f = tid + 256 * i;
-            const int r = f >> 3, kq = f & 7;
-            const long long src = row0 + r + off;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row0 + r < p.P && src >= 0 && src < p.P) {
-                v = *reinterpret_cast<const float4*>(p.X + src * p.ldx + col + kq * 4);
-                if (p.act) v = hg_lrelu4(v, p.slope);
-            }
-            ra[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < B_IT; ++i) {
-            const int f = tid + 256 * i;
-            const int r = f >> 3, kq = f & 7;
-            const int gn = col0 + r;
-            rb[i] = gn < p.N ? *reinterpret_cast<const float4*>(W + (long long)gn * p.K + k0 + kq * 4)
-                             : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto put = [&](unsigned short* S, int img, int f, const float4& v) {
-        const int r = f >> 3, kq = f & 7;
-        uint2 hi;
-        hi.x = t2_cvt_pk_bf16(v.x, v.y);
-        hi.y = t2_cvt_pk_bf16(v.z, v.w);
-        *reinterpret_cast<uint2*>(&S[r * HHLD + kq * 4]) = hi;
-        if (X3) {
-            uint2 lo;
-            lo.x = t2_cvt_pk_bf16(v.x - __uint_as_float(hi.x << 16), v.y - __uint_as_float(hi.x & 0xffff0000u));
-            lo.y = t2_cvt_pk_bf16(v.z - __uint_as_float(hi.y << 16), v.w - __uint_as_float(hi.y & 0xffff0000u));
-            *reinterpret_cast<uint2*>(&S[img + r * HHLD + kq * 4]) = lo;
-        }
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) put(As[buf], IMGA, tid + 256 * i, ra[i]);
-#pragma unroll
-        for (int i = 0; i < B_IT; ++i) put(Bs[buf], IMGB, tid + 256 * i, rb[i]);
-    };
-    auto frag = [&](const unsigned short* S, int row, int ks, int lhi_) -> hg_bf16x8 {
-        return *reinterpret_cast<const hg_bf16x8*>(&S[row * HHLD + ks * 16 + lhi_ * 8]);
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    load(0);
-    store(0);
-    __syncthreads();
-    const int l31 = lane & 31, lhi = lane >> 5;
-    int cur = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        const bool more = kt + 1 < nk;
-        if (more) load((kt + 1) * HHK);
-#pragma unroll
-        for (int ks = 0; ks < HHK / 16; ++ks) {
-            hg_bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
-#pragma unroll
-            for (int t = 0; t < TM; ++t) {
-                ah[t] = frag(As[cur], (wm * TM + t) * 32 + l31, ks, lhi);
-                if (X3) al[t] = frag(As[cur] + IMGA, (wm * TM + t) * 32 + l31, ks, lhi);
-            }
-#pragma unroll
-            for (int t = 0; t < TN; ++t) {
-                bh[t] = frag(Bs[cur], (wn * TN + t) * 32 + l31, ks, lhi);
-                if (X3) bl[t] = frag(Bs[cur] + IMGB, (wn * TN + t) * 32 + l31, ks, lhi);
-            }
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    if (X3) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                    }
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                }
-        }
-        if (more) store(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
-    }
-    hg_conv_epilogue<TM, TN>(p, acc, row0, col0, wm, wn, lane, phase);
+    const HgRows rows(p, (long long)blockIdx.x * 128, blockIdx.y * (WNW * TN * 32), blockIdx.z);
+    rm_tile_bf16<X3, WMW, WNW, TM, TN>(rows, p.W + (long long)rows.phase * p.N * p.K, p.N, p.K, rows.col0);
 }
-
-template <int WMW, int WNW, int TM, int TN>
-static void hg_launch(const HgConvParams& p, int precision, dim3 grid, hipStream_t s) {
-    if (precision == 0)
-        T2_LAUNCH((hg_conv_f32_kernel<WMW, WNW, TM, TN>), grid, dim3(256), 0, s, p);
-    else if (precision == 1)
-        T2_LAUNCH((hg_conv_bf16_kernel<true, WMW, WNW, TM, TN>), grid, dim3(256), 0, s, p);
-    else
-        T2_LAUNCH((hg_conv_bf16_kernel<false, WMW, WNW, TM, TN>), grid, dim3(256), 0, s, p);
-}
-
-#define HG_MAX_ROWS 2147483392LL        /* 2^31 - 256: the rows of the widest stage (grid.x = rows / 128) */
 
 static int hg_conv_run(HgConvParams& p, long long x_floats, long long w_floats, long long res_floats, long long out_floats,
                        long long n_rowb, int precision, void* stream) {
@@ -341,20 +152,15 @@ static int hg_conv_run(HgConvParams& p, long long x_floats, long long w_floats, 
                "hg_conv: X / W must be 16-byte aligned rows");
     T2_REQUIRE(p.ldout >= p.N && (!p.res || p.ldres >= p.N), "hg_conv: out / res rows too short");
     T2_REQUIRE(p.rdiv >= 1 && p.P % p.rdiv == 0 && n_rowb >= p.P / p.rdiv, "hg_conv: the row map does not cover the rows");
-    T2_REQUIRE(p.P * p.up <= HG_MAX_ROWS, "hg_conv: too many rows");
+    T2_REQUIRE(p.P * p.up <= T2_MAX_ROWS, "hg_conv: too many rows");
     T2_REQUIRE(x_floats >= (p.P - 1) * p.ldx + p.Cin, "hg_conv: X is shorter than its rows");
     T2_REQUIRE(w_floats >= (long long)p.up * p.N * p.K, "hg_conv: W is shorter than [phases][N][taps Cin]");
     T2_REQUIRE(out_floats >= (p.P * p.up - 1) * p.ldout + p.N, "hg_conv: out is shorter than its rows");
     T2_REQUIRE(!p.res || res_floats >= (p.P * p.up - 1) * p.ldres + p.N, "hg_conv: res is shorter than its rows");
     hipStream_t s = (hipStream_t)stream;
-    const int BN = p.N % 128 == 0 ? 128 : (p.N % 64 == 0 ? 64 : 32);
+    const int BN = rm_tile_cols(p.N);
     dim3 grid(t2_cdiv(p.P, 128), p.N / BN, p.up);
-    if (BN == 128)
-        hg_launch<2, 2, 2, 2>(p, precision, grid, s);
-    else if (BN == 64)
-        hg_launch<2, 2, 2, 1>(p, precision, grid, s);
-    else
-        hg_launch<4, 1, 1, 1>(p, precision, grid, s);
+    RM_LAUNCH_COLS(hg_conv_f32_kernel, hg_conv_bf16_kernel, BN, precision, grid, s, p);
     T2_LAUNCH_CHECK();
     return T2AMD_OK;
 }

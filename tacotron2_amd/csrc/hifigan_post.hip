@@ -8,7 +8,6 @@
 #define HG_POST_ROWS 128
 #define HG_POST_TAPS 7
 #define HG_POST_MAXC 64
-#define HG_MAX_ROWS 2147483392LL        /* 2^31 - 256, as in hifigan.hip */
 
 __device__ __forceinline__ float hg_post_lrelu(float x, float slope) { return x > 0.f ? x : x * slope; }
 
@@ -42,7 +41,7 @@ extern "C" int t2amd_hg_post_f32(const float* X, long long x_floats, long long l
                                  long long w_floats, const float* bias, float slope, const int* rowb0, const int* rowr0,
                                  long long n_rowb, int rdiv, float* out, long long T, long long out_floats, void* stream) {
     T2_REQUIRE(X && w && bias && rowb0 && rowr0 && out, "hg_post: null operand");
-    T2_REQUIRE(P > 0 && P <= HG_MAX_ROWS && C >= 1 && C <= HG_POST_MAXC, "hg_post: 1 to 64 input channels, at most 2^31 - 256 rows");
+    T2_REQUIRE(P > 0 && P <= T2_MAX_ROWS && C >= 1 && C <= HG_POST_MAXC, "hg_post: 1 to 64 input channels, at most 2^31 - 256 rows");
     T2_REQUIRE(ldx >= C && x_floats >= (P - 1) * ldx + C, "hg_post: X is shorter than its rows");
     T2_REQUIRE(w_floats >= HG_POST_TAPS * C, "hg_post: w is shorter than [7][C]");
     T2_REQUIRE(rdiv >= 1 && P % rdiv == 0 && n_rowb >= P / rdiv, "hg_post: the row map does not cover the rows");
@@ -71,7 +70,7 @@ extern "C" int t2amd_hg_pack_mel_f32(const float* mel, long long mel_floats, int
     T2_REQUIRE(B >= 1 && n_mel >= 1 && N >= 1 && P0 >= 1, "hg_pack_mel: bad dims");
     T2_REQUIRE(mel_floats >= (long long)B * n_mel * N, "hg_pack_mel: mel is shorter than (B, n_mel, N)");
     T2_REQUIRE(ldo >= n_mel && ldo % 4 == 0 && t2_aligned16(out), "hg_pack_mel: out rows must be 16-byte aligned and hold n_mel");
-    T2_REQUIRE(out_floats >= P0 * ldo && P0 * ldo <= HG_MAX_ROWS * 64, "hg_pack_mel: out is shorter than its rows");
+    T2_REQUIRE(out_floats >= P0 * ldo && P0 * ldo <= T2_MAX_ROWS * 64, "hg_pack_mel: out is shorter than its rows");
     T2_LAUNCH(hg_pack_mel_kernel, dim3(t2_cdiv(P0 * ldo, 256)), dim3(256), 0, (hipStream_t)stream, mel, n_mel, N, rowb0, rowr0, P0,
               out, ldo);
     T2_LAUNCH_CHECK();

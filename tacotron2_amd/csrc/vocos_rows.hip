@@ -9,7 +9,6 @@
 // never leaks into a halo.  No MFMA here, so the CPU suite runs this very source on the host stand-in (tests/hip_emu).
 #include "common.h"
 
-#define VC_MAX_ROWS 2147483392LL        /* 2^31 - 256, as in hifigan.hip */
 #define VC_MAX_D 512
 #define VC_MAX_TAPS 15
 #define VC_DWLN_ROWS 4                  /* waves (= rows) per workgroup */
@@ -92,7 +91,7 @@ extern "C" int t2amd_vc_dwln_f32(const float* X, long long x_floats, long long l
                                  float eps, const int* rowb0, long long n_rowb, float* out, long long ldout,
                                  long long out_floats, void* stream) {
     T2_REQUIRE(X && ln_w && ln_b && rowb0 && out, "vc_dwln: null operand");
-    T2_REQUIRE(P > 0 && P <= VC_MAX_ROWS && n_rowb >= P, "vc_dwln: the row map does not cover the rows (at most 2^31 - 256)");
+    T2_REQUIRE(P > 0 && P <= T2_MAX_ROWS && n_rowb >= P, "vc_dwln: the row map does not cover the rows (at most 2^31 - 256)");
     T2_REQUIRE(D >= 32 && D % 32 == 0 && D <= VC_MAX_D, "vc_dwln: channels must be a multiple of 32, at most 512");
     T2_REQUIRE(taps == 0 || (taps % 2 == 1 && taps <= VC_MAX_TAPS), "vc_dwln: taps must be 0 (LayerNorm alone) or odd, at most 15");
     T2_REQUIRE(taps == 0 || (w && conv_bias && w_floats >= (long long)taps * D), "vc_dwln: w is shorter than [taps][D]");
@@ -133,7 +132,7 @@ extern "C" int t2amd_vc_polar_f32(const float* Y, long long y_floats, long long 
                                   const int* rowb0, long long n_rowb, float* S, long long lds, long long s_floats,
                                   void* stream) {
     T2_REQUIRE(Y && rowb0 && S, "vc_polar: null operand");
-    T2_REQUIRE(P > 0 && P <= VC_MAX_ROWS && n_rowb >= P, "vc_polar: the row map does not cover the rows (at most 2^31 - 256)");
+    T2_REQUIRE(P > 0 && P <= T2_MAX_ROWS && n_rowb >= P, "vc_polar: the row map does not cover the rows (at most 2^31 - 256)");
     T2_REQUIRE(F >= 1 && F <= 8193 && clamp > 0.f, "vc_polar: 1 to 8193 bins, a positive clamp");
     T2_REQUIRE(ldy >= 2 * F && y_floats >= (P - 1) * ldy + 2 * F, "vc_polar: Y is shorter than its rows of 2 F values");
     T2_REQUIRE(lds >= 2 * F && lds % 2 == 0 && s_floats >= P * lds, "vc_polar: S is shorter than its rows of 2 F values (even stride)");
@@ -176,11 +175,11 @@ extern "C" int t2amd_vc_ola_f32(const float* frames, long long f_floats, long lo
                                 const int* utt, int B, int L, int hop, int trim, float* out, long long T, long long out_floats,
                                 void* stream) {
     T2_REQUIRE(frames && wsq && utt && out, "vc_ola: null operand");
-    T2_REQUIRE(P > 0 && P <= VC_MAX_ROWS && B >= 1 && B <= 65535, "vc_ola: 1 to 65535 utterances, at most 2^31 - 256 rows");
+    T2_REQUIRE(P > 0 && P <= T2_MAX_ROWS && B >= 1 && B <= 65535, "vc_ola: 1 to 65535 utterances, at most 2^31 - 256 rows");
     T2_REQUIRE(L >= 2 && L <= 16384 && hop >= 1 && hop <= L && L % hop == 0, "vc_ola: hop must divide the frame length (at most 16384)");
     T2_REQUIRE(trim >= 0 && 2 * trim >= L - hop && 2 * trim <= L, "vc_ola: trim must be (L - hop) / 2 to L / 2");
     T2_REQUIRE(ldf >= L && f_floats >= (P - 1) * ldf + L, "vc_ola: frames is shorter than its rows");
-    T2_REQUIRE(T >= 1 && T <= VC_MAX_ROWS * 256 && out_floats >= (long long)B * T, "vc_ola: out is shorter than (B, T)");
+    T2_REQUIRE(T >= 1 && T <= T2_MAX_ROWS * 256 && out_floats >= (long long)B * T, "vc_ola: out is shorter than (B, T)");
     T2_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 3u) == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0,
                "vc_ola: frames / out misaligned");
     T2_LAUNCH(vc_ola_kernel, dim3(t2_cdiv(T, 256), B), dim3(256), 0, (hipStream_t)stream, frames, ldf, P, wsq, utt, L, hop, trim,

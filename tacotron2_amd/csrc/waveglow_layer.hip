@@ -1,7 +1,11 @@
 // WaveGlow WN layer products on the MFMA (see waveglow.hip for the layout and the rest of the inference path).
 //
-// One kernel body per precision, both with 128 x 128 output tiles of 4 waves (2 x 2, 64 x 64 per wave = 2 x 2 MFMA tiles
-// of 32 x 32), A = the channel-last row image, B = weights [N][K] (K contiguous).  K is tap-major: column tap * Cin + c of
+// The tile loop itself (LDS images, K loop, MFMA nest, once per precision family) is csrc/rowmma.h, shared with hifigan.hip
+// and vocos.hip.  This file owns the parameters, how a row of A is fetched (WgRows), the three epilogues, the __global__
+// wrappers with their grid mapping, and the C entries with their checks.
+//
+// Always 128 x 128 output tiles of 4 waves (2 x 2, 64 x 64 per wave = 2 x 2 MFMA tiles of 32 x 32; columns at and beyond N
+// are masked), A = the channel-last row image, B = weights [N][K] (K contiguous).  K is tap-major: column tap * Cin + c of
 // row m reads X[(m + (tap - (taps - 1) / 2) * dil) * ldx + c].  The caller points X at the first computed row of an image
 // whose zero halo is at least dil rows deep on both sides, so no tap needs a bounds test and none crosses an utterance.
 //
@@ -20,7 +24,7 @@
 //
 // Precision 0 is the exact-f32 MFMA (v_mfma_f32_32x32x2_f32), 1 split-bf16 x 3 and 2 plain bf16 on
 // v_mfma_f32_32x32x16_bf16, with the operand splitting of gemm.hip's bf16 kernels.
-#include "common.h"
+#include "rowmma.h"
 
 struct WgLayerParams {
     const float* X;
@@ -123,194 +127,35 @@ __device__ __forceinline__ void wg_layer_epilogue(const WgLayerParams& p, f32x16
     }
 }
 
-// ---- exact f32: 128 x 128 x 16 tiles, both operands transposed into k-major LDS (row stride 132) ----------------------
-#define WBK 16
-#define WLD 132
-
-__global__ __launch_bounds__(256) void wg_layer_f32_kernel(WgLayerParams p) {
-    __shared__ __attribute__((aligned(16))) float As[2][WBK][WLD];
-    __shared__ __attribute__((aligned(16))) float Bs[2][WBK][WLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int row0 = blockIdx.y * 128, col0 = blockIdx.x * 128;
-    const int nk = p.K / WBK;
-    const int half = (p.taps - 1) / 2;
-    float4 ra[2], rb[2];
-
-    auto load = [&](int k0) {
+// The rows of one 128 x 128 tile for csrc/rowmma.h: 32-bit row arithmetic, `gm < M` the only guard (the caller's halo covers
+// every shifted row), the tap of a K-step taken once per step.
+struct WgRows {
+    const WgLayerParams& p;
+    int row0, col0, half;
+    __device__ __forceinline__ RmStep step(int k0) const {
         const int tap = k0 / p.Cin;
-        const int off = (tap - half) * p.dil;
-        const int col = k0 - tap * p.Cin;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = tid + 256 * i;
-            const int r = f >> 2, kq = f & 3;
-            const int gm = row0 + r, gn = col0 + r;
-            ra[i] = gm < p.M ? *reinterpret_cast<const float4*>(p.X + (long long)(gm + off) * p.ldx + col + kq * 4)
-                             : make_float4(0.f, 0.f, 0.f, 0.f);
-            rb[i] = gn < p.N ? *reinterpret_cast<const float4*>(p.W + (long long)gn * p.K + k0 + kq * 4)
-                             : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = tid + 256 * i;
-            const int r = f >> 2, kq = f & 3;
-            As[buf][kq * 4 + 0][r] = ra[i].x;
-            As[buf][kq * 4 + 1][r] = ra[i].y;
-            As[buf][kq * 4 + 2][r] = ra[i].z;
-            As[buf][kq * 4 + 3][r] = ra[i].w;
-            Bs[buf][kq * 4 + 0][r] = rb[i].x;
-            Bs[buf][kq * 4 + 1][r] = rb[i].y;
-            Bs[buf][kq * 4 + 2][r] = rb[i].z;
-            Bs[buf][kq * 4 + 3][r] = rb[i].w;
-        }
-    };
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    load(0);
-    store(0);
-    __syncthreads();
-    const int l31 = lane & 31, lhi = lane >> 5;
-    int cur = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        const bool more = kt + 1 < nk;
-        if (more) load((kt + 1) * WBK);
-#pragma unroll
-        for (int kk = 0; kk < WBK / 2; ++kk) {
-            const int krow = kk * 2 + lhi;
-            const float a0 = As[cur][krow][wm * 64 + l31];
-            const float a1 = As[cur][krow][wm * 64 + 32 + l31];
-            const float b0 = Bs[cur][krow][wn * 64 + l31];
-            const float b1 = Bs[cur][krow][wn * 64 + 32 + l31];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        if (more) store(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
+        return {(tap - half) * p.dil, k0 - tap * p.Cin};
     }
-    wg_layer_epilogue(p, acc, row0, col0, wm, wn, lane);
-}
+    __device__ __forceinline__ float4 a(const RmStep& s, int r, int kc) const {
+        const int gm = row0 + r;
+        return gm < p.M ? *reinterpret_cast<const float4*>(p.X + (long long)(gm + s.off) * p.ldx + s.col + kc)
+                        : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __device__ __forceinline__ void epilogue(f32x16 (&acc)[2][2], int wm, int wn, int lane) const {
+        wg_layer_epilogue(p, acc, row0, col0, wm, wn, lane);
+    }
+};
 
-// ---- split-bf16 x 3 (X3) / plain bf16: 128 x 128 x 32 tiles, K-contiguous bf16 LDS rows (stride 40) ------------------
-typedef short wg_bf16x8 __attribute__((ext_vector_type(8)));
-#define WHK 32
-#define WHLD 40
-
-__device__ __forceinline__ unsigned wg_cvt_pk_bf16(float a, float b) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
+// blockIdx.x = column tile, blockIdx.y = row tile: the column tiles of a row tile are neighbours in the launch order
+__global__ __launch_bounds__(256) void wg_layer_f32_kernel(WgLayerParams p) {
+    const WgRows rows{p, (int)blockIdx.y * 128, (int)blockIdx.x * 128, (p.taps - 1) / 2};
+    rm_tile_f32<2, 2, 2, 2>(rows, p.W, p.N, p.K, rows.col0);
 }
 
 template <bool X3>
 __global__ __launch_bounds__(256) void wg_layer_bf16_kernel(WgLayerParams p) {
-    constexpr int NH = X3 ? 2 : 1;
-    constexpr int IMG = 128 * WHLD;
-    __shared__ __attribute__((aligned(16))) unsigned short As[2][NH * IMG];
-    __shared__ __attribute__((aligned(16))) unsigned short Bs[2][NH * IMG];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int row0 = blockIdx.y * 128, col0 = blockIdx.x * 128;
-    const int nk = p.K / WHK;
-    const int half = (p.taps - 1) / 2;
-    float4 ra[4], rb[4];
-
-    auto load = [&](int k0) {
-        const int tap = k0 / p.Cin;
-        const int off = (tap - half) * p.dil;
-        const int col = k0 - tap * p.Cin;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int f = tid + 256 * i;
-            const int r = f >> 3, kq = f & 7;
-            const int gm = row0 + r, gn = col0 + r;
-            ra[i] = gm < p.M ? *reinterpret_cast<const float4*>(p.X + (long long)(gm + off) * p.ldx + col + kq * 4)
-                             : make_float4(0.f, 0.f, 0.f, 0.f);
-            rb[i] = gn < p.N ? *reinterpret_cast<const float4*>(p.W + (long long)gn * p.K + k0 + kq * 4)
-                             : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto store_one = [&](unsigned short* S, const float4 (&v)[4]) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int f = tid + 256 * i;
-            const int r = f >> 3, kq = f & 7;
-            uint2 hi;
-            hi.x = wg_cvt_pk_bf16(v[i].x, v[i].y);
-            hi.y = wg_cvt_pk_bf16(v[i].z, v[i].w);
-            *reinterpret_cast<uint2*>(&S[r * WHLD + kq * 4]) = hi;
-            if (X3) {
-                uint2 lo;
-                lo.x = wg_cvt_pk_bf16(v[i].x - __uint_as_float(hi.x << 16), v[i].y - __uint_as_float(hi.x & 0xffff0000u));
-                lo.y = wg_cvt_pk_bf16(v[i].z - __uint_as_float(hi.y << 16), v[i].w - __uint_as_float(hi.y & 0xffff0000u));
-                *reinterpret_cast<uint2*>(&S[IMG + r * WHLD + kq * 4]) = lo;
-            }
-        }
-    };
-    auto frag = [&](const unsigned short* S, int row, int ks, int lhi_) -> wg_bf16x8 {
-        return *reinterpret_cast<const wg_bf16x8*>(&S[row * WHLD + ks * 16 + lhi_ * 8]);
-    };
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    load(0);
-    store_one(As[0], ra);
-    store_one(Bs[0], rb);
-    __syncthreads();
-    const int l31 = lane & 31, lhi = lane >> 5;
-    int cur = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        const bool more = kt + 1 < nk;
-        if (more) load((kt + 1) * WHK);
-#pragma unroll
-        for (int ks = 0; ks < WHK / 16; ++ks) {
-            wg_bf16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                ah[t] = frag(As[cur], wm * 64 + t * 32 + l31, ks, lhi);
-                bh[t] = frag(Bs[cur], wn * 64 + t * 32 + l31, ks, lhi);
-                if (X3) {
-                    al[t] = frag(As[cur] + IMG, wm * 64 + t * 32 + l31, ks, lhi);
-                    bl[t] = frag(Bs[cur] + IMG, wn * 64 + t * 32 + l31, ks, lhi);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    if (X3) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                    }
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                }
-        }
-        if (more) {
-            store_one(As[cur ^ 1], ra);
-            store_one(Bs[cur ^ 1], rb);
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
-    wg_layer_epilogue(p, acc, row0, col0, wm, wn, lane);
+    const WgRows rows{p, (int)blockIdx.y * 128, (int)blockIdx.x * 128, (p.taps - 1) / 2};
+    rm_tile_bf16<X3, 2, 2, 2, 2>(rows, p.W, p.N, p.K, rows.col0);
 }
 
 extern "C" int t2amd_wg_layer_train_f32(const float* X, long long ldx, const float* W, const float* bias, int M, int N, int Cin,
@@ -349,12 +194,7 @@ extern "C" int t2amd_wg_layer_train_f32(const float* X, long long ldx, const flo
     dim3 grid(t2_cdiv(N, 128), t2_cdiv(M, 128));
     T2_REQUIRE(grid.y <= 65535, "wg_layer: too many rows");
     hipStream_t s = (hipStream_t)stream;
-    if (precision == 0)
-        T2_LAUNCH(wg_layer_f32_kernel, grid, dim3(256), 0, s, p);
-    else if (precision == 1)
-        T2_LAUNCH(wg_layer_bf16_kernel<true>, grid, dim3(256), 0, s, p);
-    else
-        T2_LAUNCH(wg_layer_bf16_kernel<false>, grid, dim3(256), 0, s, p);
+    rm_launch(precision, wg_layer_f32_kernel, wg_layer_bf16_kernel<true>, wg_layer_bf16_kernel<false>, grid, s, p);
     T2_LAUNCH_CHECK();
     return T2AMD_OK;
 }

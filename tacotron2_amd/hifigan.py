@@ -29,7 +29,7 @@ from .waveglow import PRECISIONS, fold_weight_norm
 LRELU_SLOPE = 0.1
 POST_SLOPE = 0.01                 # the reference's last leaky_relu is called without a slope: torch's default
 PRE_KERNEL = POST_KERNEL = 7
-MAX_ROWS = 2 ** 31 - 256          # the rows of the widest stage (csrc/hifigan.hip HG_MAX_ROWS)
+MAX_ROWS = 2 ** 31 - 256          # the rows of the widest stage (csrc/common.h T2_MAX_ROWS)
 MAX_CHANNELS = 512
 MAX_POST_CHANNELS = 64
 

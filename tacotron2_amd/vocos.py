@@ -31,7 +31,7 @@ EMBED_KERNEL = DW_KERNEL = 7
 LN_EPS = 1e-6
 MAG_CLAMP = 100.0
 HALO = 3                          # zero rows around every utterance: the 7-tap windows, and (n_fft - hop) / hop frames of tail
-MAX_ROWS = 2 ** 31 - 256          # csrc/vocos.hip VC_MAX_ROWS
+MAX_ROWS = 2 ** 31 - 256          # csrc/common.h T2_MAX_ROWS
 MAX_DIM = 512
 MAX_INTERMEDIATE = 2048
 MAX_N_FFT = 16384

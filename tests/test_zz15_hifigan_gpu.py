@@ -320,3 +320,19 @@ def test_waveglow_bits_equal_the_parent_commits(native_lib):
     got = mk.digests()
     assert set(got) == set(want) and len(want) == 12
     assert got == want, sorted(k for k in want if got[k] != want[k])
+
+
+# ---- the shared tile loop (csrc/rowmma.h) moves no bit of the generator --------------------------------------------------------
+def test_hifigan_bits_equal_the_digests_from_before_the_shared_tile_loop(native_lib):
+    """tests/golden/vocoder_digests.json was written by the commit before the three vocoders' tile loops became one: the small
+    generators full and ragged, V1 ragged, and hg_conv / hg_upsample alone at C = 32, 64 and 128, per precision."""
+    sys.path.insert(0, gu.GOLDEN_DIR)
+    try:
+        import make_golden_vocoder_digests as mk
+    finally:
+        sys.path.remove(gu.GOLDEN_DIR)
+    with open(os.path.join(gu.GOLDEN_DIR, "vocoder_digests.json")) as fh:
+        want = json.load(fh)["hifigan"]
+    got = mk.digests_hifigan()
+    assert set(got) == set(want) and len(want) == 51
+    assert got == want, sorted(k for k in want if got[k] != want[k])

@@ -16,6 +16,7 @@ sanity bounds 1e-4 / 3e-2.  fp32 is held to 10 x the error the float32 run of th
 the same test, which does not depend on the code under test.  With 'bf16' only the two products of every block run in bf16:
 the head product and the inverse DFT stay split-bf16, since a phase error goes straight into the waveform."""
 import functools
+import json
 import os
 import subprocess
 import sys
@@ -318,3 +319,19 @@ def test_cli_vocos_writes_wavs(native_lib, tmp_path):
     for i, n in enumerate(lens):
         sr, x = wavfile.read(os.path.join(out, "m%d.wav" % i))
         assert sr == 22050 and x.dtype == np.int16 and x.shape == (256 * n,) and np.abs(x).max() > 1000
+
+
+# ---- the shared tile loop (csrc/rowmma.h) moves no bit of the vocoder ----------------------------------------------------------
+def test_vocos_bits_equal_the_digests_from_before_the_shared_tile_loop(native_lib):
+    """tests/golden/vocoder_digests.json was written by the commit before the three vocoders' tile loops became one: 'small' and
+    'odd' full and ragged, and vc_linear's three epilogues alone at every (D, I) of DI (BN = 64, 32 and 128), per precision."""
+    sys.path.insert(0, gu.GOLDEN_DIR)
+    try:
+        import make_golden_vocoder_digests as mk
+    finally:
+        sys.path.remove(gu.GOLDEN_DIR)
+    with open(os.path.join(gu.GOLDEN_DIR, "vocoder_digests.json")) as fh:
+        want = json.load(fh)["vocos"]
+    got = mk.digests_vocos()
+    assert set(got) == set(want) and len(want) == 39
+    assert got == want, sorted(k for k in want if got[k] != want[k])
