@@ -24,7 +24,8 @@ import torch
 from torch import nn
 
 from . import native as nv
-from .waveglow import PRECISIONS, fold_weight_norm
+from .vocoder import PRECISIONS, Vocoder, checkpoint_source, packed_rows
+from .waveglow import fold_weight_norm
 
 LRELU_SLOPE = 0.1
 POST_SLOPE = 0.01                 # the reference's last leaky_relu is called without a slope: torch's default
@@ -120,7 +121,9 @@ def pack_up(weight, bias, u, ci_e, co_e):
     return wp.reshape(u, co_e, taps * ci_e), b
 
 
-class Generator(nn.Module):
+class Generator(Vocoder):
+    LABEL = 'HiFi-GAN'
+
     def __init__(self, n_mel_channels=80, upsample_initial_channel=512, upsample_rates=(8, 8, 2, 2),
                  upsample_kernel_sizes=(16, 16, 4, 4), resblock='1', resblock_kernel_sizes=(3, 7, 11),
                  resblock_dilation_sizes=None, precision='fp32'):
@@ -175,41 +178,12 @@ class Generator(nn.Module):
         self.resblocks = nn.ModuleList([block(chans[i + 1], k, d) for i in range(len(rates)) for k, d in zip(ks, dil)])
         self.conv_post = nn.Conv1d(chans[-1], 1, POST_KERNEL, padding=POST_KERNEL // 2)
         self.precision = precision
-        self.half_io = False
-        self._pack = None
-        self._plan_cache = None
 
     def config(self):
         return dict(n_mel_channels=self.n_mel_channels, upsample_initial_channel=self.upsample_initial_channel,
                     upsample_rates=list(self.upsample_rates), upsample_kernel_sizes=list(self.upsample_kernel_sizes),
                     resblock=self.resblock, resblock_kernel_sizes=list(self.resblock_kernel_sizes),
                     resblock_dilation_sizes=[tuple(d) for d in self.resblock_dilation_sizes])
-
-    # ---- precision / dtype -------------------------------------------------------------------------------------------
-    @property
-    def precision(self):
-        return self._precision
-
-    @precision.setter
-    def precision(self, p):
-        if p not in PRECISIONS:
-            raise ValueError("HiFi-GAN: precision must be one of %s, got %r" % (sorted(PRECISIONS), p))
-        self._precision = p
-
-    def half(self):
-        """f32 master weights kept; bf16 compute, float16 output."""
-        self.precision, self.half_io = 'bf16', True
-        return self
-
-    def float(self):
-        super().float()
-        self.precision, self.half_io = 'fp32', False
-        return self
-
-    def _apply(self, fn, recurse=True):
-        super()._apply(fn, recurse)
-        self._pack = self._plan_cache = None
-        return self
 
     def remove_weight_norm(self):
         """The reference's call before inference: the module is always folded, so there is nothing to remove."""
@@ -226,9 +200,8 @@ class Generator(nn.Module):
             raise ValueError("HiFi-GAN: state dict geometry does not match the module's %s: %s" % (self.config(), e))
         if cfg != self.config():
             raise ValueError("HiFi-GAN: state dict geometry %s does not match the module's %s" % (cfg, self.config()))
-        sd = {k: v.float() if torch.is_tensor(v) and v.is_floating_point() else v for k, v in sd.items()}
         self._pack = None
-        return super().load_state_dict(sd, strict=strict, assign=assign)
+        return super().load_state_dict(self._f32_state(sd), strict=strict, assign=assign)
 
     @classmethod
     def from_state_dict(cls, state_dict, precision='fp32', upsample_rates=None, resblock_dilation_sizes=None):
@@ -236,13 +209,6 @@ class Generator(nn.Module):
         m = cls(precision=precision, **config_from_state_dict(sd, upsample_rates, resblock_dilation_sizes))
         m.load_state_dict(sd)
         return m
-
-    @classmethod
-    def from_module(cls, module, precision='fp32', upsample_rates=None, resblock_dilation_sizes=None):
-        """Adopt a loaded reference generator (weight-normed or not): its weights are read once."""
-        with torch.no_grad():
-            sd = {k: v.detach().float().cpu() for k, v in module.state_dict().items()}
-        return cls.from_state_dict(sd, precision, upsample_rates, resblock_dilation_sizes)
 
     # ---- row plan -----------------------------------------------------------------------------------------------------
     def stage_scales(self):
@@ -272,16 +238,7 @@ class Generator(nn.Module):
 
     def packed_plan(self, lengths):
         """(rowb0, rowr0, offsets, P0) of the frame-level packed row space for per-utterance frame counts (host tensors)."""
-        H = self.halo_frames()
-        rowb, rowr, offs = [np.full(H, -1, np.int32)], [np.zeros(H, np.int32)], []
-        pos = H
-        for b, n in enumerate(lengths):
-            n = int(n)
-            offs.append(pos)
-            rowb += [np.full(n, b, np.int32), np.full(H, -1, np.int32)]
-            rowr += [np.arange(n, dtype=np.int32), np.zeros(H, np.int32)]
-            pos += n + H
-        return torch.from_numpy(np.concatenate(rowb)), torch.from_numpy(np.concatenate(rowr)), offs, pos
+        return packed_rows(lengths, self.halo_frames())
 
     def workspace_floats(self, P0):
         """Floats of the one allocation of a call with P0 frame-level packed rows: four stage images of the widest stage and
@@ -291,20 +248,17 @@ class Generator(nn.Module):
         return 4 * widest + P0 * _ce(self.n_mel_channels), widest
 
     def _plan(self, lens, dev):
-        key = (tuple(lens), str(dev))
-        if self._plan_cache is not None and self._plan_cache[0] == key:
-            return self._plan_cache[1]
-        rowb0, rowr0, offs, P0 = self.packed_plan(lens)
-        if P0 * self.hop > MAX_ROWS:
-            raise ValueError("HiFi-GAN: %d packed frames x %d samples per frame exceed the %d rows one call can address; "
-                             "split the batch" % (P0, self.hop, MAX_ROWS))
-        plan = (rowb0.to(dev), rowr0.to(dev), P0)
-        self._plan_cache = (key, plan)
-        return plan
+        def build():
+            rowb0, rowr0, offs, P0 = self.packed_plan(lens)
+            if P0 * self.hop > MAX_ROWS:
+                raise ValueError("HiFi-GAN: %d packed frames x %d samples per frame exceed the %d rows one call can address; "
+                                 "split the batch" % (P0, self.hop, MAX_ROWS))
+            return rowb0.to(dev), rowr0.to(dev), P0
+        return self._cached_plan((tuple(lens), str(dev)), build)
 
     # ---- device-side weight layout ------------------------------------------------------------------------------------
     def _packed(self, device):
-        key = (str(device), tuple((p.data_ptr(), p._version) for p in self.parameters()))
+        key = self._pack_key(device)
         if self._pack is not None and self._pack[0] == key:
             return self._pack[1]
 
@@ -338,26 +292,12 @@ class Generator(nn.Module):
     def infer(self, mel, lengths=None):
         """(B, n_mel, N) log-mels (float32 / float16 / bfloat16) -> (B, 1, hop N) audio (float16 after ``.half()``).
         ``lengths``: frames per utterance (ragged: each computed as if alone, zero beyond hop n_b)."""
-        dev = self.conv_pre.weight.device
-        if dev.type != 'cuda' and not nv.validate_only():
-            raise nv.NativeError("HiFi-GAN: move the module to the MI355X first (.cuda()); there is no CPU path")
-        if not torch.is_tensor(mel) or mel.dim() != 3 or mel.shape[1] != self.n_mel_channels:
-            raise ValueError("HiFi-GAN.infer: expected (B, %d, N) mels, got %s"
-                             % (self.n_mel_channels, tuple(mel.shape) if torch.is_tensor(mel) else type(mel)))
-        if mel.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise ValueError("HiFi-GAN.infer: mels must be float32, float16 or bfloat16, got %s" % mel.dtype)
-        B, nm, N = mel.shape
-        lens = [N] * B if lengths is None else [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        if B < 1 or N < 1 or len(lens) != B or min(lens) < 1 or max(lens) > N:
-            raise ValueError("HiFi-GAN.infer: lengths %s do not fit %d utterances of %d frames" % (lens, B, N))
+        dev = self._device()
+        B, nm, N, lens = self._check_mels(mel, lengths, "infer")
         prec = PRECISIONS[self.precision]
         rowb0, rowr0, P0 = self._plan(lens, dev)
         total, widest = self.workspace_floats(P0)
-        if dev.type == 'cuda':
-            free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-            if 4 * (total + B * self.hop * N) > free:
-                raise nv.NativeError("HiFi-GAN.infer: the workspace needs %.2f GB (%d packed frames) and %.2f GB are free; "
-                                     "split the batch" % (4 * total / 1e9, P0, free / 1e9))
+        self._check_free(dev, total + B * self.hop * N, total, P0, "infer")
         pk = self._packed(dev)
         x32 = mel.to(device=dev, dtype=torch.float32).contiguous()
         ws = torch.empty(total, dtype=torch.float32, device=dev)
@@ -402,7 +342,7 @@ class Generator(nn.Module):
                         nv.hg_conv(src, w, b, k, d, LRELU_SLOPE, cur, dst, 1.0, False, rowb0, scale, prec)
                         cur, cur_k = dst, dst_k
         nv.hg_post(img(3, P0 * scale, ce[-1]), pk['post'][0], pk['post'][1], POST_SLOPE, rowb0, rowr0, scale, out)
-        return out.half() if self.half_io else out
+        return self._io(out)
 
     def forward(self, mel):
         """The reference's ``forward`` is its inference."""
@@ -411,14 +351,4 @@ class Generator(nn.Module):
 
 def load_hifigan(src, precision='fp32'):
     """A Generator from a checkpoint path, a state dict, ``{'generator': state dict or module}`` or a module."""
-    if isinstance(src, str):
-        src = torch.load(src, map_location='cpu', weights_only=False)
-    if isinstance(src, dict) and 'generator' in src:
-        src = src['generator']
-    if isinstance(src, Generator):
-        return src
-    if isinstance(src, nn.Module):
-        return Generator.from_module(src, precision=precision)
-    if isinstance(src, dict):
-        return Generator.from_state_dict(src, precision=precision)
-    raise TypeError("load_hifigan: expected a path, a state dict or a module, got %s" % type(src).__name__)
+    return Generator._from_source(checkpoint_source(src, 'generator'), "load_hifigan", precision=precision)

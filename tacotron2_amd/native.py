@@ -2071,79 +2071,89 @@ def _floats(t):
     return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
 
 
+def _image(t, out=False):
+    """A row image [P][C] -> (its arguments as the hg_* / vc_* entries take them, P, C): an operand is (pointer, addressed
+    floats, row stride, rows, width), an output or a residual (pointer, row stride, addressed floats).  The entries take
+    them in this order; one that takes no width (vc_polar, vc_ola) gets the operand's first four, ``[:4]``."""
+    p, ld, P, C = _mat(t)
+    return ((p, ld, _floats(t)) if out else (p, _floats(t), ld, P, C)), P, C
+
+
+def _res(who, res, out):
+    """The arguments of the optional residual image beside out; a null image without one."""
+    if res is None:
+        return None, 0, 0                            # the triple of _image(res, True) for no image
+    r, Pr, Nr = _image(res, True)
+    if (Pr, Nr) != tuple(out.shape):
+        raise NativeError("%s: res %s beside out %s" % (who, tuple(res.shape), tuple(out.shape)))
+    return r
+
+
+def _vec(t):
+    """An optional contiguous float32 vector -> pointer or NULL."""
+    return None if t is None else ptr(_fullc(t))
+
+
 def _hg_map(rowb0, rowr0=None):
+    """The row map -> (rowb0's pointer, [rowr0's pointer,] map rows)."""
     if rowb0.dtype != torch.int32 or rowb0.dim() != 1 or not rowb0.is_contiguous():
         raise NativeError("hifigan: rowb0 must be a contiguous int32 vector")
     if rowr0 is not None and (rowr0.dtype != torch.int32 or rowr0.shape != rowb0.shape or not rowr0.is_contiguous()):
         raise NativeError("hifigan: rowr0 must be an int32 vector of rowb0's length")
-    return rowb0.numel()
+    return (ptr(rowb0, torch.int32),) + (() if rowr0 is None else (ptr(rowr0, torch.int32),)) + (rowb0.numel(),)
 
 
 def hg_conv(X, W, bias, taps, dil, slope, res, out, scale, accumulate, rowb0, rdiv, precision):
     """out [P][N] = epi(bias + the dilated `taps`-tap product of the row image X [P][Cin] with W [N][taps * Cin]), leaky-ReLU
     (`slope`; None: none) on the operand; epi: (+ res) * scale, stored or added into out; zero on rows whose frame-level row
     rowb0[p // rdiv] is negative."""
-    px, ldx, P, Cin = _mat(X)
+    x, P, Cin = _image(X)
     pw, ldw, N, K = _mat(W)
-    po, ldo, Po, No = _mat(out)
+    o, Po, No = _image(out, True)
     if K != taps * Cin or ldw != K or Po != P or No != N or (bias is not None and bias.numel() != N):
         raise NativeError("hg_conv: shape mismatch X=%s W=%s out=%s taps=%d" % (tuple(X.shape), tuple(W.shape),
                                                                                   tuple(out.shape), taps))
-    pr, ldr, nr = None, 0, 0
-    if res is not None:
-        pr, ldr, Pr, Nr = _mat(res)
-        if Pr != P or Nr != N:
-            raise NativeError("hg_conv: res %s beside out %s" % (tuple(res.shape), tuple(out.shape)))
-        nr = _floats(res)
-    n_rowb = _hg_map(rowb0)
-    _check(load().t2amd_hg_conv_f32(px, _i64(_floats(X)), _i64(ldx), _i64(P), Cin, pw, _i64(_floats(W)),
-                                    ptr(_fullc(bias)) if bias is not None else None, N, int(taps), int(dil),
-                                    0 if slope is None else 1, _F(0.0 if slope is None else slope), pr, _i64(ldr), _i64(nr),
-                                    po, _i64(ldo), _i64(_floats(out)), _F(scale), 1 if accumulate else 0,
-                                    ptr(rowb0, torch.int32), _i64(n_rowb), int(rdiv), int(precision), _stream()),
-           "t2amd_hg_conv_f32")
+    r, m = _res("hg_conv", res, out), _hg_map(rowb0)
+    _check(load().t2amd_hg_conv_f32(*x, pw, _floats(W), _vec(bias), N, int(taps), int(dil), 0 if slope is None else 1,
+                                    _F(0.0 if slope is None else slope), *r, *o, _F(scale), 1 if accumulate else 0,
+                                    *m, int(rdiv), int(precision), _stream()), "t2amd_hg_conv_f32")
 
 
 def hg_upsample(X, W, bias, ku, u, slope, out, rowb0, rdiv, precision):
     """out [u P][N] = ConvTranspose1d(kernel ku, stride u, padding (ku - u) / 2) of the row image X [P][Cin] as u polyphase
     products; W [u][N][(ku / u) * Cin] the per-phase weight slices (Generator._packed).  rdiv: that of X's rows."""
-    px, ldx, P, Cin = _mat(X)
-    po, ldo, Po, N = _mat(out)
+    x, P, Cin = _image(X)
+    o, Po, N = _image(out, True)
     if W.dim() != 3 or not W.is_contiguous() or u < 1 or ku % u or tuple(W.shape) != (u, N, ku // u * Cin) or Po != u * P \
             or (bias is not None and bias.numel() != N):
         raise NativeError("hg_upsample: shape mismatch X=%s W=%s out=%s ku=%d u=%d" % (tuple(X.shape), tuple(W.shape),
                                                                                         tuple(out.shape), ku, u))
-    n_rowb = _hg_map(rowb0)
-    _check(load().t2amd_hg_upsample_f32(px, _i64(_floats(X)), _i64(ldx), _i64(P), Cin, ptr(W), _i64(_floats(W)),
-                                        ptr(_fullc(bias)) if bias is not None else None, N, int(ku), int(u),
-                                        0 if slope is None else 1, _F(0.0 if slope is None else slope), po, _i64(ldo),
-                                        _i64(_floats(out)), ptr(rowb0, torch.int32), _i64(n_rowb), int(rdiv), int(precision),
-                                        _stream()), "t2amd_hg_upsample_f32")
+    _check(load().t2amd_hg_upsample_f32(*x, ptr(W), _floats(W), _vec(bias), N, int(ku), int(u), 0 if slope is None else 1,
+                                        _F(0.0 if slope is None else slope), *o, *_hg_map(rowb0), int(rdiv),
+                                        int(precision), _stream()), "t2amd_hg_upsample_f32")
 
 
 def hg_post(X, w, bias, slope, rowb0, rowr0, rdiv, out):
     """conv_post: out (B, 1, T)[b, 0, rowr0[f] * rdiv + p % rdiv] = tanh(bias + 7-tap product of lrelu(X [P][C]) with w [7][C])
     for the rows p of real frames f = p // rdiv."""
-    px, ldx, P, C = _mat(X)
+    x, _, C = _image(X)
     if w.dim() != 2 or not w.is_contiguous() or w.shape[1] != C or bias.numel() != 1 or out.dim() != 3 or out.shape[1] != 1:
         raise NativeError("hg_post: shape mismatch X=%s w=%s out=%s" % (tuple(X.shape), tuple(w.shape), tuple(out.shape)))
-    n_rowb = _hg_map(rowb0, rowr0)
-    _check(load().t2amd_hg_post_f32(px, _i64(_floats(X)), _i64(ldx), _i64(P), C, ptr(w), _i64(w.numel()), ptr(bias),
-                                    _F(slope), ptr(rowb0, torch.int32), ptr(rowr0, torch.int32), _i64(n_rowb), int(rdiv),
-                                    ptr(_fullc(out)), _i64(out.shape[2]), _i64(out.numel()), _stream()), "t2amd_hg_post_f32")
+    _check(load().t2amd_hg_post_f32(*x, ptr(w), w.numel(), ptr(bias), _F(slope), *_hg_map(rowb0, rowr0), int(rdiv),
+                                    ptr(_fullc(out)), out.shape[2], out.numel(), _stream()), "t2amd_hg_post_f32")
 
 
 def hg_pack_mel(mel, rowb0, rowr0, out):
     """out [P0][ldo] = the (B, n_mel, N) mels as frame-level rows: out[f][c] = mel[rowb0[f]][c][rowr0[f]], zero on halo
     rows and on the padding columns c >= n_mel."""
-    po, ldo, P0, No = _mat(out)
-    if mel.dim() != 3 or No != ldo or mel.shape[1] > ldo:
+    o, P0, No = _image(out, True)
+    if mel.dim() != 3 or No != o[1] or mel.shape[1] > No:
         raise NativeError("hg_pack_mel: mel %s into contiguous rows %s" % (tuple(mel.shape), tuple(out.shape)))
-    if _hg_map(rowb0, rowr0) != P0:
+    m = _hg_map(rowb0, rowr0)
+    if m[2] != P0:
         raise NativeError("hg_pack_mel: %d map rows for %d image rows" % (rowb0.numel(), P0))
     B, n_mel, N = mel.shape
-    _check(load().t2amd_hg_pack_mel_f32(ptr(_fullc(mel)), _i64(_floats(mel)), B, n_mel, _i64(N), ptr(rowb0, torch.int32),
-                                        ptr(rowr0, torch.int32), _i64(P0), po, int(ldo), _i64(_floats(out)), _stream()),
+    _check(load().t2amd_hg_pack_mel_f32(ptr(_fullc(mel)), _floats(mel), B, n_mel, N, *m, *o, _stream()),
            "t2amd_hg_pack_mel_f32")
 
 
@@ -2156,68 +2166,54 @@ VC_EPI = {None: 0, 'gelu': 1, 'residual': 2}
 def vc_dwln(X, w, conv_bias, ln_w, ln_b, eps, rowb0, out):
     """out [P][D] = LayerNorm_D(conv_bias + the depthwise product of the row image X [P][D] with w [taps][D]) * ln_w + ln_b;
     w None: LayerNorm of X alone.  Zero on rows whose rowb0 is negative."""
-    px, ldx, P, D = _mat(X)
-    po, ldo, Po, Do = _mat(out)
+    x, P, D = _image(X)
+    o, Po, Do = _image(out, True)
     taps = 0 if w is None else int(w.shape[0])
     if (Po, Do) != (P, D) or ln_w.numel() != D or ln_b.numel() != D or \
             (w is not None and (w.dim() != 2 or w.shape[1] != D or conv_bias is None or conv_bias.numel() != D)):
         raise NativeError("vc_dwln: shape mismatch X=%s w=%s out=%s" % (tuple(X.shape), None if w is None else tuple(w.shape),
                                                                         tuple(out.shape)))
-    n_rowb = _hg_map(rowb0)
-    _check(load().t2amd_vc_dwln_f32(px, _i64(_floats(X)), _i64(ldx), _i64(P), D, ptr(_fullc(w)) if w is not None else None,
-                                    _i64(0 if w is None else w.numel()), ptr(_fullc(conv_bias)) if w is not None else None,
-                                    taps, ptr(_fullc(ln_w)), ptr(_fullc(ln_b)), _F(eps), ptr(rowb0, torch.int32), _i64(n_rowb),
-                                    po, _i64(ldo), _i64(_floats(out)), _stream()), "t2amd_vc_dwln_f32")
+    _check(load().t2amd_vc_dwln_f32(*x, _vec(w), 0 if w is None else w.numel(), _vec(conv_bias) if w is not None else None,
+                                    taps, _vec(ln_w), _vec(ln_b), _F(eps), *_hg_map(rowb0), *o, _stream()),
+           "t2amd_vc_dwln_f32")
 
 
 def vc_linear(X, W, bias, epi, gamma, res, out, rowb0, precision):
     """out [P][N] = epi(bias + X [P][K] W [N][K]^T); epi None, 'gelu' (exact) or 'residual' (res + gamma * .; res may be
     out).  Zero on rows whose rowb0 is negative."""
-    px, ldx, P, K = _mat(X)
+    x, P, K = _image(X)
     pw, ldw, N, Kw = _mat(W)
-    po, ldo, Po, No = _mat(out)
+    o, Po, No = _image(out, True)
     if epi not in VC_EPI:
         raise NativeError("vc_linear: epi must be None, 'gelu' or 'residual', got %r" % (epi,))
     if Kw != K or ldw != K or Po != P or No != N or (bias is not None and bias.numel() != N) or \
             (gamma is not None and gamma.numel() != N):
         raise NativeError("vc_linear: shape mismatch X=%s W=%s out=%s" % (tuple(X.shape), tuple(W.shape), tuple(out.shape)))
-    pr, ldr, nr = None, 0, 0
-    if res is not None:
-        pr, ldr, Pr, Nr = _mat(res)
-        if Pr != P or Nr != N:
-            raise NativeError("vc_linear: res %s beside out %s" % (tuple(res.shape), tuple(out.shape)))
-        nr = _floats(res)
-    n_rowb = _hg_map(rowb0)
-    _check(load().t2amd_vc_linear_f32(px, _i64(_floats(X)), _i64(ldx), _i64(P), K, pw, _i64(_floats(W)),
-                                      ptr(_fullc(bias)) if bias is not None else None, N, VC_EPI[epi],
-                                      ptr(_fullc(gamma)) if gamma is not None else None, pr, _i64(ldr), _i64(nr), po, _i64(ldo),
-                                      _i64(_floats(out)), ptr(rowb0, torch.int32), _i64(n_rowb), int(precision), _stream()),
-           "t2amd_vc_linear_f32")
+    r, m = _res("vc_linear", res, out), _hg_map(rowb0)
+    _check(load().t2amd_vc_linear_f32(*x, pw, _floats(W), _vec(bias), N, VC_EPI[epi], _vec(gamma), *r, *o, *m,
+                                      int(precision), _stream()), "t2amd_vc_linear_f32")
 
 
 def vc_polar(Y, F, clamp, rowb0, S):
     """S [P][lds] interleaved (re, im) = min(exp(Y[:, k]), clamp) (cos, sin)(Y[:, F + k]) for k < F, zero pad columns and
     halo rows."""
-    py, ldy, P, Ny = _mat(Y)
-    ps, lds, Ps, Ns = _mat(S)
-    if Ps != P or Ny < 2 * F or Ns != lds or Ns < 2 * F:
+    y, P, Ny = _image(Y)
+    s, Ps, Ns = _image(S, True)
+    if Ps != P or Ny < 2 * F or Ns != s[1] or Ns < 2 * F:
         raise NativeError("vc_polar: shape mismatch Y=%s S=%s F=%d" % (tuple(Y.shape), tuple(S.shape), F))
-    n_rowb = _hg_map(rowb0)
-    _check(load().t2amd_vc_polar_f32(py, _i64(_floats(Y)), _i64(ldy), _i64(P), int(F), _F(clamp), ptr(rowb0, torch.int32),
-                                     _i64(n_rowb), ps, _i64(lds), _i64(_floats(S)), _stream()), "t2amd_vc_polar_f32")
+    _check(load().t2amd_vc_polar_f32(*y[:4], int(F), _F(clamp), *_hg_map(rowb0), *s, _stream()), "t2amd_vc_polar_f32")
 
 
 def vc_ola(frames, wsq, utt, hop, trim, out):
     """out (B, 1, T) = the overlap-add of the frame rows [P][L] of every utterance (utt int32 [B][2]: first row, frames),
     trimmed by `trim` samples, over the overlap-added squared window wsq [L]; zero beyond each utterance."""
-    pf, ldf, P, L = _mat(frames)
+    f, _, L = _image(frames)
     if out.dim() != 3 or out.shape[1] != 1 or utt.dtype != torch.int32 or tuple(utt.shape) != (out.shape[0], 2) or \
             not utt.is_contiguous() or wsq.numel() != L:
         raise NativeError("vc_ola: shape mismatch frames=%s wsq=%s utt=%s out=%s" % (tuple(frames.shape), tuple(wsq.shape),
                                                                                       tuple(utt.shape), tuple(out.shape)))
-    _check(load().t2amd_vc_ola_f32(pf, _i64(_floats(frames)), _i64(ldf), _i64(P), ptr(_fullc(wsq)), ptr(utt, torch.int32),
-                                   int(out.shape[0]), int(L), int(hop), int(trim), ptr(_fullc(out)), _i64(out.shape[2]),
-                                   _i64(out.numel()), _stream()), "t2amd_vc_ola_f32")
+    _check(load().t2amd_vc_ola_f32(*f[:4], _vec(wsq), ptr(utt, torch.int32), int(out.shape[0]), int(L), int(hop),
+                                   int(trim), ptr(_fullc(out)), out.shape[2], out.numel(), _stream()), "t2amd_vc_ola_f32")
 
 
 # ----------------------------------------------------------------------------

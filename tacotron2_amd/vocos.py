@@ -25,7 +25,7 @@ from torch import nn
 
 from . import native as nv
 from .hifigan import _ce, pack_conv
-from .waveglow import PRECISIONS
+from .vocoder import PRECISIONS, Vocoder, checkpoint_source, packed_rows
 
 EMBED_KERNEL = DW_KERNEL = 7
 LN_EPS = 1e-6
@@ -121,7 +121,9 @@ def inverse_basis(window):
     return out.float()
 
 
-class Vocos(nn.Module):
+class Vocos(Vocoder):
+    LABEL = 'Vocos'
+
     def __init__(self, n_mel_channels=80, dim=512, intermediate_dim=1536, num_layers=8, n_fft=1024, hop_length=256,
                  padding='same', precision='fp32'):
         super().__init__()
@@ -152,41 +154,12 @@ class Vocos(nn.Module):
         self.backbone = Backbone(self.n_mel_channels, D, I, self.num_layers)
         self.head = Head(D, L)
         self.precision = precision
-        self.half_io = False
-        self._pack = None
-        self._plan_cache = None
 
     hop_length = property(lambda self: self.hop)
 
     def config(self):
         return dict(n_mel_channels=self.n_mel_channels, dim=self.dim, intermediate_dim=self.intermediate_dim,
                     num_layers=self.num_layers, n_fft=self.n_fft, hop_length=self.hop, padding=self.padding)
-
-    # ---- precision / dtype -------------------------------------------------------------------------------------------
-    @property
-    def precision(self):
-        return self._precision
-
-    @precision.setter
-    def precision(self, p):
-        if p not in PRECISIONS:
-            raise ValueError("Vocos: precision must be one of %s, got %r" % (sorted(PRECISIONS), p))
-        self._precision = p
-
-    def half(self):
-        """f32 master weights kept; bf16 compute in the blocks, float16 output."""
-        self.precision, self.half_io = 'bf16', True
-        return self
-
-    def float(self):
-        super().float()
-        self.precision, self.half_io = 'fp32', False
-        return self
-
-    def _apply(self, fn, recurse=True):
-        super()._apply(fn, recurse)
-        self._pack = self._plan_cache = None
-        return self
 
     # ---- loading ------------------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict, strict=True, assign=False):
@@ -195,9 +168,8 @@ class Vocos(nn.Module):
         cfg = config_from_state_dict(sd, hop_length=self.hop, padding=self.padding)
         if cfg != self.config():
             raise ValueError("Vocos: state dict geometry %s does not match the module's %s" % (cfg, self.config()))
-        sd = {k: v.float() if torch.is_tensor(v) and v.is_floating_point() else v for k, v in sd.items()}
         self._pack = None
-        return super().load_state_dict(sd, strict=strict, assign=assign)
+        return super().load_state_dict(self._f32_state(sd), strict=strict, assign=assign)
 
     @classmethod
     def from_state_dict(cls, state_dict, precision='fp32', hop_length=None, padding='same'):
@@ -205,13 +177,6 @@ class Vocos(nn.Module):
         m = cls(precision=precision, **config_from_state_dict(sd, hop_length, padding))
         m.load_state_dict(sd)
         return m
-
-    @classmethod
-    def from_module(cls, module, precision='fp32', hop_length=None, padding='same'):
-        """Adopt a loaded reference model: its weights are read once."""
-        with torch.no_grad():
-            sd = {k: v.detach().float().cpu() for k, v in module.state_dict().items()}
-        return cls.from_state_dict(sd, precision, hop_length, padding)
 
     # ---- row plan -----------------------------------------------------------------------------------------------------
     def trim(self):
@@ -231,17 +196,9 @@ class Vocos(nn.Module):
 
     def packed_plan(self, lengths):
         """(rowb0, rowr0, utt, offsets, P) of the packed row space for per-utterance frame counts (host tensors)."""
-        H = HALO
-        rowb, rowr, offs = [np.full(H, -1, np.int32)], [np.zeros(H, np.int32)], []
-        pos = H
-        for b, n in enumerate(lengths):
-            n = int(n)
-            offs.append(pos)
-            rowb += [np.full(n, b, np.int32), np.full(H, -1, np.int32)]
-            rowr += [np.arange(n, dtype=np.int32), np.zeros(H, np.int32)]
-            pos += n + H
+        rowb, rowr, offs, P = packed_rows(lengths, HALO)
         utt = torch.tensor([[o, int(n)] for o, n in zip(offs, lengths)], dtype=torch.int32)
-        return torch.from_numpy(np.concatenate(rowb)), torch.from_numpy(np.concatenate(rowr)), utt, offs, pos
+        return rowb, rowr, utt, offs, P
 
     def row_widths(self):
         """Floats per packed row of the workspace regions: mels, two D-wide images, the intermediate, head, spectrum, frames."""
@@ -253,20 +210,17 @@ class Vocos(nn.Module):
         return P * sum(self.row_widths())
 
     def _plan(self, lens, dev):
-        key = (tuple(lens), str(dev))
-        if self._plan_cache is not None and self._plan_cache[0] == key:
-            return self._plan_cache[1]
-        rowb0, rowr0, utt, offs, P = self.packed_plan(lens)
-        if P > MAX_ROWS:
-            raise ValueError("Vocos: %d packed frames exceed the %d rows one call can address; split the batch" % (P, MAX_ROWS))
-        plan = (rowb0.to(dev), rowr0.to(dev), utt.to(dev), P)
-        self._plan_cache = (key, plan)
-        return plan
+        def build():
+            rowb0, rowr0, utt, offs, P = self.packed_plan(lens)
+            if P > MAX_ROWS:
+                raise ValueError("Vocos: %d packed frames exceed the %d rows one call can address; split the batch"
+                                 % (P, MAX_ROWS))
+            return rowb0.to(dev), rowr0.to(dev), utt.to(dev), P
+        return self._cached_plan((tuple(lens), str(dev)), build)
 
     # ---- device-side weight layout ------------------------------------------------------------------------------------
     def _packed(self, device):
-        tensors = list(self.parameters()) + list(self.buffers())
-        key = (str(device), tuple((p.data_ptr(), p._version) for p in tensors))
+        key = self._pack_key(device)
         if self._pack is not None and self._pack[0] == key:
             return self._pack[1]
 
@@ -300,18 +254,8 @@ class Vocos(nn.Module):
     def infer(self, mel, lengths=None):
         """(B, n_mel, N) log-mels (float32 / float16 / bfloat16) -> (B, 1, hop N) audio ('center': hop (N - 1); float16 after
         ``.half()``).  ``lengths``: frames per utterance (ragged: each computed as if alone, zero beyond its samples)."""
-        dev = self.head.out.weight.device
-        if dev.type != 'cuda' and not nv.validate_only():
-            raise nv.NativeError("Vocos: move the module to the MI355X first (.cuda()); there is no CPU path")
-        if not torch.is_tensor(mel) or mel.dim() != 3 or mel.shape[1] != self.n_mel_channels:
-            raise ValueError("Vocos.infer: expected (B, %d, N) mels, got %s"
-                             % (self.n_mel_channels, tuple(mel.shape) if torch.is_tensor(mel) else type(mel)))
-        if mel.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise ValueError("Vocos.infer: mels must be float32, float16 or bfloat16, got %s" % mel.dtype)
-        B, nm, N = mel.shape
-        lens = [N] * B if lengths is None else [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        if B < 1 or N < 1 or len(lens) != B or min(lens) < 1 or max(lens) > N:
-            raise ValueError("Vocos.infer: lengths %s do not fit %d utterances of %d frames" % (lens, B, N))
+        dev = self._device()
+        B, nm, N, lens = self._check_mels(mel, lengths, "infer")
         T = self.samples(N)
         if T < 1 or B > 65535:
             raise ValueError("Vocos.infer: %d utterances of %d frames give %d samples with padding %r (1 to 65535 utterances, "
@@ -320,20 +264,12 @@ class Vocos(nn.Module):
         head_prec = min(prec, 1)
         rowb0, rowr0, utt, P = self._plan(lens, dev)
         total = self.workspace_floats(P)
-        if dev.type == 'cuda':
-            free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-            if 4 * (total + B * T) > free:
-                raise nv.NativeError("Vocos.infer: the workspace needs %.2f GB (%d packed frames) and %.2f GB are free; "
-                                     "split the batch" % (4 * total / 1e9, P, free / 1e9))
+        self._check_free(dev, total + B * T, total, P, "infer")
         pk = self._packed(dev)
         x32 = mel.to(device=dev, dtype=torch.float32).contiguous()
         ws = torch.empty(total, dtype=torch.float32, device=dev)
         out = torch.empty(B, 1, T, dtype=torch.float32, device=dev)
-        regions, pos = [], 0
-        for wdt in self.row_widths():
-            regions.append(ws[pos:pos + P * wdt].view(P, wdt))
-            pos += P * wdt
-        mel_cl, x, t, h, y, spec, frames = regions
+        mel_cl, x, t, h, y, spec, frames = self._regions(ws, P, self.row_widths())
         nv.hg_pack_mel(x32, rowb0, rowr0, mel_cl)
         nv.hg_conv(mel_cl, pk['embed'][0], pk['embed'][1], EMBED_KERNEL, 1, None, None, t, 1.0, False, rowb0, 1, prec)
         nv.vc_dwln(t, None, None, pk['norm'][0], pk['norm'][1], LN_EPS, rowb0, x)
@@ -346,7 +282,7 @@ class Vocos(nn.Module):
         nv.vc_polar(y, self.n_fft // 2 + 1, MAG_CLAMP, rowb0, spec)
         nv.vc_linear(spec, pk['basis'], None, None, None, None, frames, rowb0, head_prec)
         nv.vc_ola(frames, pk['wsq'], utt, self.hop, self.trim(), out)
-        return out.half() if self.half_io else out
+        return self._io(out)
 
     def forward(self, mel):
         """The reference's ``decode`` of mel features."""
@@ -357,10 +293,7 @@ def load_vocos(src, precision=None, hop_length=None, padding=None):
     """A Vocos from a checkpoint path, a state dict, ``{'state_dict': state dict}`` or a module.  ``precision`` defaults to
     'fp32', ``hop_length`` to n_fft / 4, ``padding`` to 'same'.  A Vocos instance is returned as it is, with ``precision``
     set when given; a hop or padding other than its own is refused (they are part of its geometry)."""
-    if isinstance(src, str):
-        src = torch.load(src, map_location='cpu', weights_only=False)
-    if isinstance(src, dict) and 'state_dict' in src and not torch.is_tensor(src['state_dict']):
-        src = src['state_dict']
+    src = checkpoint_source(src, 'state_dict')
     if isinstance(src, Vocos):
         if (hop_length is not None and int(hop_length) != src.hop) or (padding is not None and padding != src.padding):
             raise ValueError("load_vocos: the module has hop %d and padding %r, asked for hop %s and padding %r"
@@ -370,8 +303,4 @@ def load_vocos(src, precision=None, hop_length=None, padding=None):
         return src
     precision = 'fp32' if precision is None else precision
     padding = 'same' if padding is None else padding
-    if isinstance(src, nn.Module):
-        return Vocos.from_module(src, precision=precision, hop_length=hop_length, padding=padding)
-    if isinstance(src, dict):
-        return Vocos.from_state_dict(src, precision=precision, hop_length=hop_length, padding=padding)
-    raise TypeError("load_vocos: expected a path, a state dict or a module, got %s" % type(src).__name__)
+    return Vocos._from_source(src, "load_vocos", precision=precision, hop_length=hop_length, padding=padding)

@@ -39,8 +39,8 @@ from torch import nn
 
 from . import native as nv
 from .audio import STFT
+from .vocoder import PRECISIONS, Vocoder, checkpoint_source, host_lengths, packed_rows
 
-PRECISIONS = {'fp32': 0, 'bf16x3': 1, 'bf16': 2}
 HOP = 256                    # upsample stride (NVIDIA's ConvTranspose1d(n_mel, n_mel, 1024, stride=256))
 UP_KERNEL = 1024
 
@@ -134,7 +134,9 @@ class WN(nn.Module):
             self.res_skip_layers.append(nn.Conv1d(n_channels, 2 * n_channels if i < n_layers - 1 else n_channels, 1))
 
 
-class WaveGlow(nn.Module):
+class WaveGlow(Vocoder):
+    LABEL = 'WaveGlow'
+
     def __init__(self, n_mel_channels, n_flows, n_group, n_early_every, n_early_size, WN_config, precision='fp32',
                  weight_norm=False):
         super().__init__()
@@ -170,33 +172,10 @@ class WaveGlow(nn.Module):
             self.flow_channels.append(n_rem)
         self.n_remaining_channels = n_rem
         self.precision = precision
-        self.half_io = False
-        self._pack = None
         self.weight_norm = False
         self._wn = None
         if weight_norm:
             self.apply_weight_norm()
-
-    # ---- precision / dtype -------------------------------------------------------------------------------------------
-    @property
-    def precision(self):
-        return self._precision
-
-    @precision.setter
-    def precision(self, p):
-        if p not in PRECISIONS:
-            raise ValueError("WaveGlow: precision must be one of %s, got %r" % (sorted(PRECISIONS), p))
-        self._precision = p
-
-    def half(self):
-        """f32 master weights kept; bf16 compute, float16 output."""
-        self.precision, self.half_io = 'bf16', True
-        return self
-
-    def float(self):
-        super().float()
-        self.precision, self.half_io = 'fp32', False
-        return self
 
     # ---- loading ------------------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict, strict=True, assign=False):
@@ -215,9 +194,8 @@ class WaveGlow(nn.Module):
         got = {k: cfg[k] for k in mine}
         if got != mine:
             raise ValueError("WaveGlow: state dict geometry %s does not match the module's %s" % (got, mine))
-        sd = {k: v.float() if torch.is_tensor(v) and v.is_floating_point() else v for k, v in sd.items()}
         self._pack = None
-        return super().load_state_dict(sd, strict=strict, assign=assign)
+        return super().load_state_dict(self._f32_state(sd), strict=strict, assign=assign)
 
     @classmethod
     def from_state_dict(cls, state_dict, precision='fp32', weight_norm=False):
@@ -232,13 +210,6 @@ class WaveGlow(nn.Module):
         m = cls(precision=precision, **config_from_state_dict(sd))
         m.load_state_dict(sd)
         return m.apply_weight_norm() if weight_norm else m
-
-    @classmethod
-    def from_module(cls, module, precision='fp32', weight_norm=False):
-        """Adopt a loaded NVIDIA WaveGlow (weight-normed or not): its weights are read once."""
-        with torch.no_grad():
-            sd = {k: v.detach().float().cpu() for k, v in module.state_dict().items()}
-        return cls.from_state_dict(sd, precision=precision, weight_norm=weight_norm)
 
     # ---- the g / v parametrisation ------------------------------------------------------------------------------------
     def _wn_modules(self):
@@ -303,7 +274,6 @@ class WaveGlow(nn.Module):
 
     def _apply(self, fn, recurse=True):
         super()._apply(fn, recurse)
-        self._pack = None
         if getattr(self, 'weight_norm', False):
             self._wn_flatten()                         # .cuda() / .to() gave every parameter an allocation of its own
         return self
@@ -363,15 +333,12 @@ class WaveGlow(nn.Module):
 
     # ---- device-side weight layout ------------------------------------------------------------------------------------
     def _packed(self, device):
-        # torch's version counters see in-place optimiser steps; FusedAdam writes through raw pointers and bumps the
-        # engine's weight generation instead
-        from .engine import _PACK_GEN
-        key = (_PACK_GEN[0], str(device), tuple((p.data_ptr(), p._version) for p in self.parameters()))
+        key = self._pack_key(device)
         if self._pack is not None and self._pack[0] == key:
             return self._pack[1]
         if self.weight_norm:
             self._wn_fold()
-            key = (key[0], key[1], tuple((p.data_ptr(), p._version) for p in self.parameters()))
+            key = self._pack_key(device)
         C, L, G, nm = self.n_channels, self.n_layers, self.n_group, self.n_mel_channels
         taps = UP_KERNEL // HOP
         with torch.no_grad():
@@ -438,32 +405,25 @@ class WaveGlow(nn.Module):
 
     def packed_plan(self, lengths):
         """(rowb, rowr, offsets, P) of the packed row space for per-utterance frame counts `lengths` (host tensors)."""
-        H, spf = self.halo(), HOP // self.n_group
-        rowb, rowr, offs = [np.full(H, -1, np.int32)], [np.zeros(H, np.int32)], []
-        pos = H
-        for b, n in enumerate(lengths):
-            R = spf * int(n)
-            offs.append(pos)
-            rowb += [np.full(R, b, np.int32), np.full(H, -1, np.int32)]
-            rowr += [np.arange(R, dtype=np.int32), np.zeros(H, np.int32)]
-            pos += R + H
-        return torch.from_numpy(np.concatenate(rowb)), torch.from_numpy(np.concatenate(rowr)), offs, pos
+        return packed_rows([HOP // self.n_group * int(n) for n in lengths], self.halo())
+
+    def _plan(self, dev, rows, frames=None):
+        """(rowb, rowr on the device, offsets, P): ``packed_plan(rows)``, or with ``frames`` ``forward_plan(rows, frames)``,
+        built and uploaded once while the same direction, lengths and device repeat.  The cache, the caller and the state
+        kept for a backward pass hold the same tensors and the same list: read-only for all of them."""
+        def build():
+            rowb, rowr, offs, P = self.packed_plan(rows) if frames is None else self.forward_plan(rows, frames)
+            return rowb.to(dev), rowr.to(dev), offs, P
+        return self._cached_plan((frames is None, tuple(rows), None if frames is None else tuple(frames), str(dev)), build)
 
     def _workspace(self, P, B, N, dev):
         """One allocation per call: cond_g [P][G n_mel] (zeroed) | cnd [P][2CL] | h (zeroed), acts, skip [P][C] |
         audio [P][G] | mel_cl [B N][n_mel]."""
         C, L, G, nm = self.n_channels, self.n_layers, self.n_group, self.n_mel_channels
-        sizes = [P * G * nm, P * 2 * C * L, P * C, P * C, P * C, P * G, B * N * nm]
-        ws = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-        parts, o = [], 0
-        for s in sizes:
-            parts.append(ws[o:o + s])
-            o += s
-        cond_g = parts[0].view(P, G * nm)
-        cnd = parts[1].view(P, 2 * C * L)
-        h, acts, skip = (t.view(P, C) for t in parts[2:5])
-        audio = parts[5].view(P, G)
-        mel_cl = parts[6].view(B * N, nm)
+        widths = [G * nm, 2 * C * L, C, C, C, G]
+        ws = torch.empty(P * sum(widths) + B * N * nm, dtype=torch.float32, device=dev)
+        cond_g, cnd, h, acts, skip, audio = self._regions(ws, P, widths)
+        mel_cl = ws[P * sum(widths):].view(B * N, nm)
         cond_g.zero_()
         h.zero_()
         return cond_g, cnd, h, acts, skip, audio, mel_cl
@@ -473,17 +433,8 @@ class WaveGlow(nn.Module):
         """(B, n_mel, N) mels (float32 / float16 / bfloat16) -> (B, 256 N) audio (float16 after ``.half()``).
         ``lengths``: frames per utterance (ragged: each computed as if alone, zero beyond 256 n_b); ``z``: the noise
         tensors in ``noise_shapes`` order instead of drawing them."""
-        dev = self.upsample.weight.device
-        if dev.type != 'cuda' and not nv.validate_only():
-            raise nv.NativeError("WaveGlow: move the module to the MI355X first (.cuda()); there is no CPU path")
-        if spect.dim() != 3 or spect.shape[1] != self.n_mel_channels:
-            raise ValueError("WaveGlow.infer: expected (B, %d, N) mels, got %s" % (self.n_mel_channels, tuple(spect.shape)))
-        if spect.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise ValueError("WaveGlow.infer: mels must be float32, float16 or bfloat16, got %s" % spect.dtype)
-        B, nm, N = spect.shape
-        lens = [N] * B if lengths is None else [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        if len(lens) != B or min(lens) < 1 or max(lens) > N:
-            raise ValueError("WaveGlow.infer: lengths %s do not fit %d utterances of %d frames" % (lens, B, N))
+        dev = self._device()
+        B, nm, N, lens = self._check_mels(spect, lengths, "infer")
         shapes = self.noise_shapes(B, N)
         if z is None:
             z = [torch.empty(s, dtype=torch.float32, device=dev).normal_() for s in shapes]
@@ -495,8 +446,7 @@ class WaveGlow(nn.Module):
         prec = PRECISIONS[self.precision]
         pk = self._packed(dev)
         C, L, G, H = self.n_channels, self.n_layers, self.n_group, self.halo()
-        rowb, rowr, offs, P = self.packed_plan(lens)
-        rowb, rowr = rowb.to(dev), rowr.to(dev)
+        rowb, rowr, offs, P = self._plan(dev, lens)
         mel = spect.to(device=dev, dtype=torch.float32).contiguous()
 
         cond_g, cnd, h, acts, skip, audio, mel_cl = self._workspace(P, B, N, dev)
@@ -529,8 +479,7 @@ class WaveGlow(nn.Module):
                        start_w=nxt['start_w'] if nxt else None, start_b=nxt['start_b'] if nxt else None,
                        h=h if nxt else None, out=out if k == 0 else None)
             zi += 1 if early else 0
-        return out.half() if self.half_io else out
-
+        return self._io(out)
 
     # ---- forward direction: audio -> latents ----------------------------------------------------------------------------
     def early_outputs(self):
@@ -554,36 +503,21 @@ class WaveGlow(nn.Module):
         """(rowb, rowr, offsets, P) of the packed row space of the forward direction: utterance b holds ``rows[b]`` real rows
         in a slot of ``frames[b]`` whole mel frames (hop / n_group rows each, what the upsample product writes); the rows of
         the last partial frame beyond ``rows[b]`` are marked like halo rows, so they are never computed into h or read back."""
-        H, spf = self.halo(), HOP // self.n_group
-        rowb, rowr, offs = [np.full(H, -1, np.int32)], [np.zeros(H, np.int32)], []
-        pos = H
-        for b, (R, nf) in enumerate(zip(rows, frames)):
-            pad = spf * int(nf) - int(R) + H
-            offs.append(pos)
-            rowb += [np.full(R, b, np.int32), np.full(pad, -1, np.int32)]
-            rowr += [np.arange(R, dtype=np.int32), np.zeros(pad, np.int32)]
-            pos += R + pad
-        return torch.from_numpy(np.concatenate(rowb)), torch.from_numpy(np.concatenate(rowr)), offs, pos
+        return packed_rows(rows, self.halo(), [HOP // self.n_group * int(nf) for nf in frames])
 
     def _forward(self, spect, audio, lengths, who, save=False):
         """-> (z (B, n_group, T') f32, log_s of all flows (B, sum_k n_half_k, T') f32, rows per utterance (host list),
         the state kept for the backward pass (``save``) or None)."""
-        dev = self.upsample.weight.device
-        if dev.type != 'cuda' and not nv.validate_only():
-            raise nv.NativeError("WaveGlow: move the module to the MI355X first (.cuda()); there is no CPU path")
-        if not torch.is_tensor(spect) or spect.dim() != 3 or spect.shape[1] != self.n_mel_channels:
-            raise ValueError("WaveGlow.%s: expected (B, %d, N) mels, got %s"
-                             % (who, self.n_mel_channels, tuple(spect.shape) if torch.is_tensor(spect) else type(spect)))
-        if not torch.is_tensor(audio) or audio.dim() != 2 or audio.shape[0] != spect.shape[0]:
+        dev = self._device()
+        B, nm, N, _ = self._check_mels(spect, None, who)
+        if not torch.is_tensor(audio) or audio.dim() != 2 or audio.shape[0] != B:
             raise ValueError("WaveGlow.%s: expected (B, T) audio for %d mels, got %s"
-                             % (who, spect.shape[0], tuple(audio.shape) if torch.is_tensor(audio) else type(audio)))
-        for name, t in (("mels", spect), ("audio", audio)):
-            if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-                raise ValueError("WaveGlow.%s: %s must be float32, float16 or bfloat16, got %s" % (who, name, t.dtype))
-        B, nm, N = spect.shape
+                             % (who, B, tuple(audio.shape) if torch.is_tensor(audio) else type(audio)))
+        if audio.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError("WaveGlow.%s: audio must be float32, float16 or bfloat16, got %s" % (who, audio.dtype))
         T = audio.shape[1]
         C, L, G, H = self.n_channels, self.n_layers, self.n_group, self.halo()
-        lens = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        lens = host_lengths(lengths, B, T)
         if len(lens) != B or min(lens) < 1 or max(lens) > T:
             raise ValueError("WaveGlow.%s: lengths %s do not fit %d utterances of %d samples" % (who, lens, B, T))
         if any(t % G for t in lens):
@@ -597,8 +531,7 @@ class WaveGlow(nn.Module):
         frames = [-(-t // HOP) for t in lens]             # mel frames at or past ceil(T_b / 256) cannot reach the audio
         prec = PRECISIONS[self.precision]
         pk = self._packed(dev)
-        rowb, rowr, offs, P = self.forward_plan(rows, frames)
-        rowb, rowr = rowb.to(dev), rowr.to(dev)
+        rowb, rowr, offs, P = self._plan(dev, rows, frames)
         mel = spect.to(device=dev, dtype=torch.float32).contiguous()
         wav = audio.to(device=dev, dtype=torch.float32).contiguous()
 
@@ -1049,14 +982,5 @@ class Denoiser(nn.Module):
 def load_waveglow(src, precision='fp32', weight_norm=False):
     """A WaveGlow from a checkpoint path, a state dict, ``{'model': state dict or module}`` or a module.
     ``weight_norm=True`` keeps ``weight_g`` / ``weight_v`` (a module to go on training); the default folds them."""
-    if isinstance(src, str):
-        src = torch.load(src, map_location='cpu', weights_only=False)
-    if isinstance(src, dict) and 'model' in src:
-        src = src['model']
-    if isinstance(src, WaveGlow):
-        return src
-    if isinstance(src, nn.Module):
-        return WaveGlow.from_module(src, precision=precision, weight_norm=weight_norm)
-    if isinstance(src, dict):
-        return WaveGlow.from_state_dict(src, precision=precision, weight_norm=weight_norm)
-    raise TypeError("load_waveglow: expected a path, a state dict or a module, got %s" % type(src).__name__)
+    return WaveGlow._from_source(checkpoint_source(src, 'model'), "load_waveglow", precision=precision,
+                                 weight_norm=weight_norm)

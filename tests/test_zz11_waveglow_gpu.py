@@ -110,6 +110,30 @@ def test_ragged_equals_alone_bitwise(native_lib, prec):
         assert rel < REL['fp32']
 
 
+def test_repeated_lengths_reuse_the_row_map_bitwise(native_lib):
+    """The module keeps its last row map (direction, lengths, device) on the device: a call that finds its own map, after
+    calls with other lengths and in the other direction, gives the bits of a fresh module's single call."""
+    _, wg = _models(SMALL, seed=25)
+    G, N, lens = wg.n_group, 40, [1, 7, 40]
+    mel = _mel(3, N, 26)
+    z = _noise(wg, 3, N, 27)
+    wav = (torch.randn(3, 40 * G, generator=torch.Generator().manual_seed(28)) * 0.1).to(DEV)
+    samples = [G * n for n in lens]
+    first = wg.infer(mel, 0.666, lengths=lens, z=z)
+    other = wg.infer(mel, 0.666, lengths=[40, 40, 40], z=z)
+    third = wg.infer(mel, 0.666, lengths=lens, z=z)
+    assert torch.equal(third, first) and not torch.equal(other, first)
+    alone = _models(SMALL, seed=25)[1].infer(mel, 0.666, lengths=lens, z=z)
+    assert torch.equal(first, alone) and torch.equal(third, alone)
+    n_first = wg.nll(mel, wav, lengths=samples)
+    n_other = wg.nll(mel, wav, lengths=[40 * G] * 3)
+    n_third = wg.nll(mel, wav, lengths=samples)
+    assert torch.equal(n_third, n_first) and not torch.equal(n_other, n_first)
+    n_alone = _models(SMALL, seed=25)[1].nll(mel, wav, lengths=samples)
+    assert torch.equal(n_first, n_alone) and torch.equal(n_third, n_alone)
+    assert torch.equal(wg.infer(mel, 0.666, lengths=lens, z=z), alone)          # back in the first direction
+
+
 def test_more_than_65535_rows(native_lib):
     ref, wg = _models(SMALL, seed=12)
     N = 2100                                     # 67,200 rows
