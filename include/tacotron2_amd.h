@@ -1189,6 +1189,49 @@ int t2amd_vc_polar_f32(const float* Y, long long y_floats, long long ldy, long l
 int t2amd_vc_ola_f32(const float* frames, long long f_floats, long long ldf, long long P, const float* wsq, const int* utt,
                      int B, int L, int hop, int trim, float* out, long long T, long long out_floats, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Vocos vocoder, the row kernels of the backward pass (csrc/vocos_bwd.hip; Vocos.generate).  The dense data gradients are
+ * t2amd_vc_linear_f32 against transposed weight images, the weight gradients t2amd_gemm_f32.  Same row space and rules as
+ * above: every entry writes all rows of its outputs and zero on halo rows.  A sum over rows leaves as partial slots, one
+ * per t2amd_vc_bwd_slot_rows() consecutive rows (slot s covers rows [s rows, (s + 1) rows)); t2amd_wg_partial_sum_f32 adds
+ * the ceil(P / rows) slots in order, so two calls give the same bits.  All images 16-byte aligned, row strides multiples
+ * of 4, D a multiple of 32 up to 512.
+ * ------------------------------------------------------------------------------------ */
+int t2amd_vc_bwd_slot_rows(void);
+/* d_frames[p][t] = d_audio[b][s - trim] / sum_j wsq[s - j hop] with b = rowb0[p], s = rowr0[p] hop + t, where 0 <= s - trim <
+ * min(T, hop (n_b - 1) + L - 2 trim); zero elsewhere and on halo rows.  The sum is t2amd_vc_ola_f32's.  L a multiple of 4. */
+int t2amd_vc_ola_bwd_f32(const float* d_audio, long long T, long long a_floats, const float* wsq, const int* utt, int B,
+                         const int* rowb0, const int* rowr0, long long n_rowb, long long P, int L, int hop, int trim,
+                         float* d_frames, long long ldf, long long f_floats, void* stream);
+/* From Y[p] = [m | ph] and d_S[p] = interleaved (d_re, d_im), with e = exp m, mag = min(e, clamp):
+ *   d_Y[p][k] = e <= clamp ? mag (cos ph d_re + sin ph d_im) : 0,  d_Y[p][F + k] = mag (cos ph d_im - sin ph d_re),
+ * zero in the columns 2 F <= c < N. */
+int t2amd_vc_polar_bwd_f32(const float* Y, long long y_floats, long long ldy, long long P, int F, float clamp, const float* dS,
+                           long long ds_floats, long long lds, const int* rowb0, long long n_rowb, float* dY, long long lddy,
+                           long long dy_floats, int N, void* stream);
+/* d_H[p][c] *= Phi(U[p][c]) + U[p][c] phi(U[p][c]) (the derivative of the exact GELU), in place; I a multiple of 32. */
+int t2amd_vc_gelu_bwd_f32(const float* U, long long u_floats, long long ldu, long long P, int I, const int* rowb0,
+                          long long n_rowb, float* dH, long long ldh, long long dh_floats, void* stream);
+/* partial[slot][c] = sum_r d_X[r][c] Y2[r][c], then Y2[r][c] = gamma[c] d_X[r][c] (in place). */
+int t2amd_vc_gamma_bwd_f32(const float* dX, long long dx_floats, long long lddx, long long P, int D, const float* gamma,
+                           const int* rowb0, long long n_rowb, float* Y2, long long ldy, long long y_floats, float* partial,
+                           long long partial_floats, void* stream);
+/* Backward of t2amd_vc_dwln_f32's LayerNorm with G = d_out: y and xh = (y - mean) rstd are recomputed from X (w, conv_bias,
+ * taps as in the forward; taps at most 7 here),
+ *   d_Z[p][c] = rstd (ln_w[c] G[p][c] - mean_c(ln_w G[p]) - xh[p][c] mean_c(ln_w G[p] xh[p])),
+ *   partial[slot] = [sum_r G[r][c] xh[r][c] (D) | sum_r G[r][c] (D)].   d_Z may be G, must not be X. */
+int t2amd_vc_ln_bwd_f32(const float* X, long long x_floats, long long ldx, long long P, int D, const float* w, long long w_floats,
+                        const float* conv_bias, int taps, const float* ln_w, float eps, const int* rowb0, long long n_rowb,
+                        const float* G, long long ldg, long long g_floats, float* dZ, long long lddz, long long dz_floats,
+                        float* partial, long long partial_floats, void* stream);
+/* Backward of the depthwise convolution over the finished d_Z image, half = (taps - 1) / 2:
+ *   d_X[p][c] = res[p][c] + sum_t w[t D + c] d_Z[p + half - t][c]    (res may be NULL or d_X)
+ *   partial[slot] = [sum_r d_Z[r][c] X[r + t - half][c] (taps x D) | sum_r d_Z[r][c] (D)].   d_X must not be d_Z or X. */
+int t2amd_vc_dw_bwd_f32(const float* dZ, long long dz_floats, long long lddz, long long P, int D, const float* X,
+                        long long x_floats, long long ldx, const float* w, long long w_floats, int taps, const int* rowb0,
+                        long long n_rowb, const float* res, long long ldres, long long res_floats, float* dX, long long lddx,
+                        long long dx_floats, float* partial, long long partial_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -296,6 +296,8 @@ SYMBOLS = [
     "t2amd_loss_workspace_doubles", "t2amd_tacotron2_loss_fwd_f32", "t2amd_tacotron2_loss_bwd_f32",
     "t2amd_hg_conv_f32", "t2amd_hg_upsample_f32", "t2amd_hg_post_f32", "t2amd_hg_pack_mel_f32",
     "t2amd_vc_dwln_f32", "t2amd_vc_linear_f32", "t2amd_vc_polar_f32", "t2amd_vc_ola_f32",
+    "t2amd_vc_bwd_slot_rows", "t2amd_vc_ola_bwd_f32", "t2amd_vc_polar_bwd_f32", "t2amd_vc_gelu_bwd_f32", "t2amd_vc_gamma_bwd_f32",
+    "t2amd_vc_ln_bwd_f32", "t2amd_vc_dw_bwd_f32",
 ]
 
 _P, _I, _L, _F, _UL = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_ulonglong
@@ -430,6 +432,13 @@ def _argtypes():
         "t2amd_vc_linear_f32": [_P, _L, _L, _L, _I, _P, _L, _P, _I, _I, _P, _P, _L, _L, _P, _L, _L, _P, _L, _I, _P],
         "t2amd_vc_polar_f32": [_P, _L, _L, _L, _I, _F, _P, _L, _P, _L, _L, _P],
         "t2amd_vc_ola_f32": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _I, _P, _L, _L, _P],
+        "t2amd_vc_bwd_slot_rows": [],
+        "t2amd_vc_ola_bwd_f32": [_P, _L, _L, _P, _P, _I, _P, _P, _L, _L, _I, _I, _I, _P, _L, _L, _P],
+        "t2amd_vc_polar_bwd_f32": [_P, _L, _L, _L, _I, _F, _P, _L, _L, _P, _L, _P, _L, _L, _I, _P],
+        "t2amd_vc_gelu_bwd_f32": [_P, _L, _L, _L, _I, _P, _L, _P, _L, _L, _P],
+        "t2amd_vc_gamma_bwd_f32": [_P, _L, _L, _L, _I, _P, _P, _L, _P, _L, _L, _P, _L, _P],
+        "t2amd_vc_ln_bwd_f32": [_P, _L, _L, _L, _I, _P, _L, _P, _I, _P, _F, _P, _L, _P, _L, _L, _P, _L, _L, _P, _L, _P],
+        "t2amd_vc_dw_bwd_f32": [_P, _L, _L, _L, _I, _P, _L, _L, _P, _L, _I, _P, _L, _P, _L, _L, _P, _L, _L, _P, _L, _P],
     }
 
 
@@ -2214,6 +2223,101 @@ def vc_ola(frames, wsq, utt, hop, trim, out):
                                                                                       tuple(utt.shape), tuple(out.shape)))
     _check(load().t2amd_vc_ola_f32(*f[:4], _vec(wsq), ptr(utt, torch.int32), int(out.shape[0]), int(L), int(hop),
                                    int(trim), ptr(_fullc(out)), out.shape[2], out.numel(), _stream()), "t2amd_vc_ola_f32")
+
+
+# ---- the backward pass's row kernels (csrc/vocos_bwd.hip) -----------------------------------------------------------------
+def vc_bwd_slot_rows():
+    """Consecutive rows per partial slot of the vc_*_bwd column sums."""
+    return int(load().t2amd_vc_bwd_slot_rows())
+
+
+def vc_bwd_slots(P):
+    """Partial slots of a [P][.] image: what ``wg_partial_sum`` adds in order."""
+    return -(-int(P) // vc_bwd_slot_rows())
+
+
+def _vc_partial(who, partial, floats):
+    """The partial-slot buffer's (pointer, floats); a null buffer is left to the entry to refuse."""
+    if partial is None:
+        return None, 0
+    if partial.dim() != 1 or not partial.is_contiguous() or partial.numel() < floats:
+        raise NativeError("%s: partial is shorter than its slots: %d floats, %d needed" % (who, partial.numel(), floats))
+    return ptr(partial), partial.numel()
+
+
+def vc_ola_bwd(d_audio, wsq, utt, rowb0, rowr0, hop, trim, d_frames):
+    """d_frames [P][L] = the gradient of ``vc_ola``'s frame rows from d_audio (B, 1, T)."""
+    f, P, L = _image(d_frames, True)
+    if d_audio.dim() != 3 or d_audio.shape[1] != 1 or utt.dtype != torch.int32 or tuple(utt.shape) != (d_audio.shape[0], 2) or \
+            not utt.is_contiguous() or wsq.numel() != L:
+        raise NativeError("vc_ola_bwd: shape mismatch d_audio=%s wsq=%s utt=%s d_frames=%s"
+                          % (tuple(d_audio.shape), tuple(wsq.shape), tuple(utt.shape), tuple(d_frames.shape)))
+    m = _hg_map(rowb0, rowr0)
+    _check(load().t2amd_vc_ola_bwd_f32(ptr(_fullc(d_audio)), d_audio.shape[2], d_audio.numel(), _vec(wsq), ptr(utt, torch.int32),
+                                       int(d_audio.shape[0]), *m, P, int(L), int(hop), int(trim), *f, _stream()),
+           "t2amd_vc_ola_bwd_f32")
+
+
+def vc_polar_bwd(Y, F, clamp, dS, rowb0, dY):
+    """dY [P][N] = [d_m | d_p | 0] from the kept head rows Y [P][>= 2F] and dS [P][>= 2F] interleaved (d_re, d_im)."""
+    y, P, Ny = _image(Y)
+    s, Ps, Ns = _image(dS)
+    o, Po, No = _image(dY, True)
+    if Ps != P or Po != P or Ny < 2 * F or Ns < 2 * F or No < 2 * F:
+        raise NativeError("vc_polar_bwd: shape mismatch Y=%s dS=%s dY=%s F=%d" % (tuple(Y.shape), tuple(dS.shape),
+                                                                                   tuple(dY.shape), F))
+    _check(load().t2amd_vc_polar_bwd_f32(*y[:4], int(F), _F(clamp), s[0], s[1], s[2], *_hg_map(rowb0), *o, int(No), _stream()),
+           "t2amd_vc_polar_bwd_f32")
+
+
+def vc_gelu_bwd(U, rowb0, dH):
+    """dH [P][I] *= GELU'(U [P][I]), in place; zero on halo rows."""
+    u, P, I = _image(U)
+    o, Po, Io = _image(dH, True)
+    if (Po, Io) != (P, I):
+        raise NativeError("vc_gelu_bwd: shape mismatch U=%s dH=%s" % (tuple(U.shape), tuple(dH.shape)))
+    _check(load().t2amd_vc_gelu_bwd_f32(*u, *_hg_map(rowb0), *o, _stream()), "t2amd_vc_gelu_bwd_f32")
+
+
+def vc_gamma_bwd(dX, gamma, rowb0, Y2, partial):
+    """partial [slots][D] = the column partials of sum_r dX Y2; then Y2 = gamma dX in place."""
+    x, P, D = _image(dX)
+    o, Po, Do = _image(Y2, True)
+    if (Po, Do) != (P, D) or gamma.numel() != D:
+        raise NativeError("vc_gamma_bwd: shape mismatch dX=%s gamma=%s Y2=%s" % (tuple(dX.shape), tuple(gamma.shape),
+                                                                                  tuple(Y2.shape)))
+    _check(load().t2amd_vc_gamma_bwd_f32(*x, _vec(gamma), *_hg_map(rowb0), *o, *_vc_partial("vc_gamma_bwd", partial, vc_bwd_slots(P) * D),
+                                         _stream()), "t2amd_vc_gamma_bwd_f32")
+
+
+def vc_ln_bwd(X, w, conv_bias, ln_w, eps, rowb0, G, dZ, partial):
+    """dZ [P][D] = the gradient of ``vc_dwln``'s LayerNorm input from G = d_out (dZ may be G); partial [slots][2 D] = the
+    column partials of the norm's weight | bias gradients."""
+    x, P, D = _image(X)
+    g, Pg, Dg = _image(G)
+    o, Po, Do = _image(dZ, True)
+    taps = 0 if w is None else int(w.shape[0])
+    if (Pg, Dg) != (P, D) or (Po, Do) != (P, D) or ln_w.numel() != D or \
+            (w is not None and (w.dim() != 2 or w.shape[1] != D or conv_bias is None or conv_bias.numel() != D)):
+        raise NativeError("vc_ln_bwd: shape mismatch X=%s w=%s G=%s dZ=%s" % (tuple(X.shape), None if w is None else
+                                                                               tuple(w.shape), tuple(G.shape), tuple(dZ.shape)))
+    _check(load().t2amd_vc_ln_bwd_f32(*x, _vec(w), 0 if w is None else w.numel(), _vec(conv_bias) if w is not None else None,
+                                      taps, _vec(ln_w), _F(eps), *_hg_map(rowb0), g[0], g[2], g[1], *o,
+                                      *_vc_partial("vc_ln_bwd", partial, vc_bwd_slots(P) * 2 * D), _stream()), "t2amd_vc_ln_bwd_f32")
+
+
+def vc_dw_bwd(dZ, X, w, rowb0, res, dX, partial):
+    """dX [P][D] = res + the transposed depthwise product of dZ with w [taps][D] (res None or dX); partial
+    [slots][taps + 1][D] = the column partials of the tap | bias gradients."""
+    z, P, D = _image(dZ)
+    x, Px, Dx = _image(X)
+    o, Po, Do = _image(dX, True)
+    if (Px, Dx) != (P, D) or (Po, Do) != (P, D) or w.dim() != 2 or w.shape[1] != D:
+        raise NativeError("vc_dw_bwd: shape mismatch dZ=%s X=%s w=%s dX=%s" % (tuple(dZ.shape), tuple(X.shape), tuple(w.shape),
+                                                                                tuple(dX.shape)))
+    r = _res("vc_dw_bwd", res, dX)
+    _check(load().t2amd_vc_dw_bwd_f32(*z, x[0], x[1], x[2], _vec(w), w.numel(), int(w.shape[0]), *_hg_map(rowb0), *r, *o,
+                                      *_vc_partial("vc_dw_bwd", partial, vc_bwd_slots(P) * (int(w.shape[0]) + 1) * D), _stream()), "t2amd_vc_dw_bwd_f32")
 
 
 # ----------------------------------------------------------------------------

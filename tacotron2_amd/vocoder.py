@@ -46,6 +46,25 @@ def checkpoint_source(src, key):
     return src
 
 
+def _splitk(M, N, K):
+    """Split count of a weight-gradient product [M][N] over K rows: about two workgroups of 128 x 128 per compute unit,
+    at least 512 rows per slice."""
+    tiles = -(-M // 128) * -(-N // 128)
+    return max(1, min(-(-512 // tiles), K // 512, 64))
+
+
+def _wgrad(out, A, Bm, prec, partials):
+    """out [M][N] = A^T . Bm over the rows of A [K][M] and Bm [K][N] (halo rows are zero in one of them), split-K in a
+    fixed order."""
+    K, M = A.shape
+    s = _splitk(M, Bm.shape[1], K)
+    if s == 1:
+        nv.gemm(out, A, Bm, a_km=True, b_kn=True, fast=prec)
+    else:
+        nv.gemm(out, A, Bm, a_km=True, b_kn=True, splitk=s, partials=partials, fast=prec)
+        nv.splitk_reduce2d(partials, s, out)
+
+
 class Vocoder(nn.Module):
     """Base of the three vocoder modules.  ``LABEL`` names the model in every error text; a subclass has ``n_mel_channels``
     and ``from_state_dict(state_dict, precision, ...)``."""

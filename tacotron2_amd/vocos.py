@@ -1,8 +1,9 @@
-"""Vocos vocoder (Siuzdak 2023) on the MI355X: mel -> waveform at the frame rate, inference only.
+"""Vocos vocoder (Siuzdak 2023) on the MI355X: mel -> waveform at the frame rate, inference and a backward pass.
 
     vc = load_vocos("vocos_mel_22khz.pt").cuda().eval()   # a state dict, {'state_dict': ...} or a module
     audio = vc(mel)                                         # (B, 80, N) log-mels -> (B, 1, 256 N) float32
     audio = vc.infer(mel, lengths=frames)                   # ragged: every utterance as if alone, zero beyond hop n_b
+    audio = vc.generate(mel); loss(audio).backward()        # infer's bits with a grad_fn: gradients of every parameter (and mel)
 
 A ConvNeXt stack on D-channel frame rows, one linear head that predicts log-magnitude and phase, one inverse STFT: nothing
 runs at the sample rate before the overlap-add.  The module keeps the published names (``backbone.embed``, ``backbone.norm``,
@@ -18,6 +19,11 @@ Per call: mel packing, embed, LayerNorm; per block three launches (dwconv + Laye
 the residual); LayerNorm, head, polar, inverse DFT, overlap-add.  One workspace allocation per call; the layer loop does no
 allocation, copy or host synchronisation and has no loop over utterances.  The arithmetic is restated in float64 torch by
 tests/vocos_ref.py; DESIGN.md section 12 has the layout.
+
+``generate`` is ``infer`` as one autograd function: it keeps ``saved_state_bytes(P)`` in one allocation (the mel rows, every
+LayerNorm input, every block's normalised rows and GELU output, the head rows) and its backward runs the row kernels of
+csrc/vocos_bwd.hip between ``vc_linear`` products against transposed weight images and fixed-order split-K weight-gradient
+products; the pre-GELU rows and the pre-gamma ``pwconv2`` output are recomputed, one product each.
 """
 import numpy as np
 import torch
@@ -25,7 +31,7 @@ from torch import nn
 
 from . import native as nv
 from .hifigan import _ce, pack_conv
-from .vocoder import PRECISIONS, Vocoder, checkpoint_source, packed_rows
+from .vocoder import PRECISIONS, Vocoder, checkpoint_source, packed_rows, _splitk, _wgrad
 
 EMBED_KERNEL = DW_KERNEL = 7
 LN_EPS = 1e-6
@@ -154,6 +160,7 @@ class Vocos(Vocoder):
         self.backbone = Backbone(self.n_mel_channels, D, I, self.num_layers)
         self.head = Head(D, L)
         self.precision = precision
+        self._pack_t = None
 
     hop_length = property(lambda self: self.hop)
 
@@ -287,6 +294,235 @@ class Vocos(Vocoder):
     def forward(self, mel):
         """The reference's ``decode`` of mel features."""
         return self.infer(mel)
+
+    # ---- training: infer with a backward pass ---------------------------------------------------------------------------
+    def saved_row_widths(self):
+        """Floats per packed row of what ``generate`` keeps: the mel rows, embed's output, the input of every block and of
+        the final LayerNorm (L + 1 images), per block the normalised rows and the GELU output, the final LayerNorm's output
+        and the head rows."""
+        D, I, L = self.dim, self.intermediate_dim, self.num_layers
+        return [_ce(self.n_mel_channels), D] + [D] * (L + 1) + [D] * L + [I] * L + [D, _pad_cols(self.n_fft + 2)]
+
+    def saved_state_bytes(self, P):
+        """Bytes ``generate`` keeps between its forward and its backward for P packed rows, in one allocation:
+        4 P (ce(n_mel) + (2 L + 3) D + L I + head columns)."""
+        return 4 * int(P) * sum(self.saved_row_widths())
+
+    def _fwd_widths(self):
+        """The forward's workspace beside the kept state: spectrum and frames."""
+        return [-(-(self.n_fft + 2) // 32) * 32, self.n_fft]
+
+    def _check_state(self, need, extra, free, P):
+        """Refuse a ``generate`` whose kept state (``need`` bytes) plus ``extra`` bytes of workspace and output do not fit."""
+        if need + extra > free:
+            raise nv.NativeError("Vocos.generate: the state kept for the backward pass needs %.2f GB (%d packed rows x %d "
+                                 "floats) and %.2f GB are free; use a smaller batch or shorter segments"
+                                 % (need / 1e9, P, sum(self.saved_row_widths()), free / 1e9))
+
+    def generate(self, mel, lengths=None):
+        """``infer`` with a backward pass: the same launches, so the same bits, as a float32 tensor with a ``grad_fn`` when
+        gradients are enabled and a parameter or ``mel`` requires grad.  ``backward()`` gives every parameter that requires
+        grad its float32 gradient (``head.istft.window`` is a buffer and gets none) and ``mel`` its own, zero beyond each
+        utterance's frames.  ``precision`` selects the compute of the backward's products as of the forward's; the head, the
+        inverse DFT and their backward stay at f32 or split-bf16.  Training keeps float32 in and out: a ``.half()`` module is
+        refused.  ``saved_state_bytes(P)`` are kept in one allocation; a state that does not fit is refused before any launch.
+        Under ``torch.no_grad()`` this is ``infer``."""
+        if self.half_io:
+            raise ValueError("Vocos.generate: the module was set to .half(); training keeps float32 in and out (call .float() "
+                             "and choose the compute with precision='bf16')")
+        params = list(self.parameters())
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in params) or (torch.is_tensor(mel) and mel.requires_grad)):
+            return _Generate.apply(self, mel, lengths, *params)
+        return self.infer(mel, lengths)
+
+    def _generate_forward(self, mel, lengths):
+        """``infer``'s launches with their row images kept -> (audio, kept state)."""
+        dev = self._device()
+        B, nm, N, lens = self._check_mels(mel, lengths, "generate")
+        T = self.samples(N)
+        if T < 1 or B > 65535:
+            raise ValueError("Vocos.generate: %d utterances of %d frames give %d samples with padding %r (1 to 65535 "
+                             "utterances, at least one sample)" % (B, N, T, self.padding))
+        prec = PRECISIONS[self.precision]
+        head_prec = min(prec, 1)
+        rowb0, rowr0, utt, P = self._plan(lens, dev)
+        L = self.num_layers
+        need, total = self.saved_state_bytes(P), P * sum(self._fwd_widths())
+        if dev.type == 'cuda':
+            free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+            self._check_state(need, 4 * (total + B * T), free, P)
+        pk = self._packed(dev)
+        x32 = mel.detach().to(device=dev, dtype=torch.float32).contiguous()
+        state = torch.empty(need // 4, dtype=torch.float32, device=dev)
+        ws = torch.empty(total, dtype=torch.float32, device=dev)
+        out = torch.empty(B, 1, T, dtype=torch.float32, device=dev)
+        kept = self._regions(state, P, self.saved_row_widths())
+        mel_cl, e, xs, ts, hs, tf, y = kept[0], kept[1], kept[2:L + 3], kept[L + 3:2 * L + 3], kept[2 * L + 3:3 * L + 3], \
+            kept[3 * L + 3], kept[3 * L + 4]
+        spec, frames = self._regions(ws, P, self._fwd_widths())
+        nv.hg_pack_mel(x32, rowb0, rowr0, mel_cl)
+        nv.hg_conv(mel_cl, pk['embed'][0], pk['embed'][1], EMBED_KERNEL, 1, None, None, e, 1.0, False, rowb0, 1, prec)
+        nv.vc_dwln(e, None, None, pk['norm'][0], pk['norm'][1], LN_EPS, rowb0, xs[0])
+        for i, blk in enumerate(pk['blocks']):
+            nv.vc_dwln(xs[i], blk['dw'][0], blk['dw'][1], blk['norm'][0], blk['norm'][1], LN_EPS, rowb0, ts[i])
+            nv.vc_linear(ts[i], blk['pw1'][0], blk['pw1'][1], 'gelu', None, None, hs[i], rowb0, prec)
+            nv.vc_linear(hs[i], blk['pw2'][0], blk['pw2'][1], 'residual', blk['gamma'], xs[i], xs[i + 1], rowb0, prec)
+        nv.vc_dwln(xs[L], None, None, pk['final'][0], pk['final'][1], LN_EPS, rowb0, tf)
+        nv.vc_linear(tf, pk['head'][0], pk['head'][1], None, None, None, y, rowb0, head_prec)
+        nv.vc_polar(y, self.n_fft // 2 + 1, MAG_CLAMP, rowb0, spec)
+        nv.vc_linear(spec, pk['basis'], None, None, None, None, frames, rowb0, head_prec)
+        nv.vc_ola(frames, pk['wsq'], utt, self.hop, self.trim(), out)
+        sv = dict(state=state, mel_cl=mel_cl, e=e, xs=xs, ts=ts, hs=hs, tf=tf, y=y, pk=pk, prec=prec, rowb0=rowb0, rowr0=rowr0,
+                  utt=utt, P=P, B=B, N=N, T=T, lens=lens, mel_dtype=mel.dtype, key=self._pack[0])
+        return out, sv
+
+    def _packed_t(self, device, pk, key):
+        """The transposed weight images of the backward's data-gradient products, built once per weight state: from the
+        forward's packed image ``pk`` and under the forward's ``key``."""
+        if self._pack_t is not None and self._pack_t[0] == key:
+            return self._pack_t[1]
+        with torch.no_grad():
+            ce, D = _ce(self.n_mel_channels), self.dim
+            w = pk['embed'][0].view(D, EMBED_KERNEL, ce)                      # d_mel[r] = sum_t d_e[r - (t - 3)] W[:, t, :]
+            pt = dict(basis=pk['basis'].t().contiguous(), head=pk['head'][0].t().contiguous(),
+                      embed=w.flip(1).permute(2, 1, 0).reshape(ce, EMBED_KERNEL * D).contiguous(),
+                      blocks=[(blk['pw1'][0].t().contiguous(), blk['pw2'][0].t().contiguous()) for blk in pk['blocks']])
+        self._pack_t = (key, pt)
+        return pt
+
+    def _grad_layout(self, B=0, N=0):
+        """(floats, {parameter name: (offset, shape)}) of the flat gradient buffer, every tensor at a multiple of 4 floats; a
+        LayerNorm's weight and bias are neighbours (one ordered pass sums both).  'mel' (B, n_mel, N) comes last when asked
+        for."""
+        lay, o = {}, 0
+        for name, p in self.named_parameters():
+            lay[name] = (o, tuple(p.shape))
+            o += -(-p.numel() // 4) * 4
+        if B:
+            lay['mel'] = (o, (B, self.n_mel_channels, N))
+            o += -(-B * self.n_mel_channels * N // 4) * 4
+        return o, lay
+
+    def _bwd_sizes(self, P, B, N, want_mel):
+        """Floats of the regions of the backward's one workspace."""
+        D, I, L, ce = self.dim, self.intermediate_dim, self.n_fft, _ce(self.n_mel_channels)
+        nh, ns, two_f = _pad_cols(L + 2), -(-(L + 2) // 32) * 32, L + 2
+        slots = nv.vc_bwd_slots(P)
+        M = P - 2 * HALO
+        sk = max(_splitk(D, I, P) * D * I, _splitk(two_f, D, P) * two_f * D, _splitk(D, ce, M) * D * ce)
+        sizes = dict(d_frames=P * L, d_spec=P * ns, d_y=P * nh, da=P * D, db=P * D, y2=P * D, u=P * I, dh=P * I,
+                     partial=slots * (DW_KERNEL + 1) * D, small=(DW_KERNEL + 1) * D, wpart=sk, g_in=D * EMBED_KERNEL * ce,
+                     ws64=2 * 2 * 64 * max(I, nh, D), d_mel_cl=P * ce if want_mel else 0, d_mel_rows=B * N * ce if want_mel else 0)
+        return {k: -(-v // 4) * 4 for k, v in sizes.items()}
+
+    def _backward(self, sv, d_audio, want_mel):
+        """The backward pass over the kept state -> {parameter name (and 'mel'): gradient, a view of one flat buffer}."""
+        D, I, L, nm = self.dim, self.intermediate_dim, self.num_layers, self.n_mel_channels
+        ce, two_f, F = _ce(nm), self.n_fft + 2, self.n_fft // 2 + 1
+        pk, prec, rowb0, rowr0, P, B, N = sv['pk'], sv['prec'], sv['rowb0'], sv['rowr0'], sv['P'], sv['B'], sv['N']
+        head_prec = min(prec, 1)
+        dev = rowb0.device
+        if self._pack_key(dev) != sv['key']:
+            raise RuntimeError("Vocos.generate: a parameter was modified between this forward and its backward (an optimiser "
+                               "step or an in-place edit); the kept state belongs to the earlier weights")
+        pt = self._packed_t(dev, pk, sv['key'])
+        d_audio = d_audio.to(device=dev, dtype=torch.float32).contiguous()
+        total, lay = self._grad_layout(B if want_mel else 0, N)
+        sizes = self._bwd_sizes(P, B, N, want_mel)
+        gout = torch.empty(total, dtype=torch.float32, device=dev)
+        bw = torch.empty(sum(sizes.values()), dtype=torch.float32, device=dev)
+        gv = {name: gout[o:o + int(np.prod(shape))].view(shape) for name, (o, shape) in lay.items()}
+        r, o = {}, 0
+        for k, n in sizes.items():
+            r[k] = bw[o:o + n]
+            o += n
+        ns = -(-two_f // 32) * 32
+        d_frames, d_spec, d_y = r['d_frames'].view(P, self.n_fft), r['d_spec'].view(P, ns), r['d_y'].view(P, -1)
+        da, db, y2 = r['da'].view(P, D), r['db'].view(P, D), r['y2'].view(P, D)
+        u, dh = r['u'].view(P, I), r['dh'].view(P, I)
+        partial, small, wpart, ws64 = r['partial'], r['small'], r['wpart'], r['ws64'].view(torch.float64)
+        slots = nv.vc_bwd_slots(P)
+
+        def norm_grads(name):
+            o = lay[name + '.weight'][0]
+            nv.wg_partial_sum(partial, slots, 2 * D, gout[o:o + 2 * D])
+
+        nv.vc_ola_bwd(d_audio, pk['wsq'], sv['utt'], rowb0, rowr0, self.hop, self.trim(), d_frames)
+        nv.vc_linear(d_frames, pt['basis'], None, None, None, None, d_spec, rowb0, head_prec)
+        nv.vc_polar_bwd(sv['y'], F, MAG_CLAMP, d_spec, rowb0, d_y)
+        _wgrad(gv['head.out.weight'], d_y[:, :two_f], sv['tf'], head_prec, wpart)
+        nv.colsum(d_y[:, :two_f], ws64, gv['head.out.bias'])
+        nv.vc_linear(d_y, pt['head'], None, None, None, None, db, rowb0, head_prec)
+        nv.vc_ln_bwd(sv['xs'][L], None, None, pk['final'][0], LN_EPS, rowb0, db, da, partial)
+        norm_grads('backbone.final_layer_norm')
+        for i in reversed(range(L)):
+            blk, (w1t, w2t), pre = pk['blocks'][i], pt['blocks'][i], 'backbone.convnext.%d.' % i
+            x, t, h = sv['xs'][i], sv['ts'][i], sv['hs'][i]
+            # da = the gradient of the block's output; the residual passes it on, gamma scales it into pwconv2
+            nv.vc_linear(h, blk['pw2'][0], blk['pw2'][1], None, None, None, y2, rowb0, prec)
+            nv.vc_gamma_bwd(da, blk['gamma'], rowb0, y2, partial)
+            nv.wg_partial_sum(partial, slots, D, gv[pre + 'gamma'])
+            _wgrad(gv[pre + 'pwconv2.weight'], y2, h, prec, wpart)
+            nv.colsum(y2, ws64, gv[pre + 'pwconv2.bias'])
+            nv.vc_linear(y2, w2t, None, None, None, None, dh, rowb0, prec)
+            nv.vc_linear(t, blk['pw1'][0], blk['pw1'][1], None, None, None, u, rowb0, prec)
+            nv.vc_gelu_bwd(u, rowb0, dh)
+            _wgrad(gv[pre + 'pwconv1.weight'], dh, t, prec, wpart)
+            nv.colsum(dh, ws64, gv[pre + 'pwconv1.bias'])
+            nv.vc_linear(dh, w1t, None, None, None, None, db, rowb0, prec)
+            nv.vc_ln_bwd(x, blk['dw'][0], blk['dw'][1], blk['norm'][0], LN_EPS, rowb0, db, db, partial)
+            norm_grads(pre + 'norm')
+            nv.vc_dw_bwd(db, x, blk['dw'][0], rowb0, da, da, partial)
+            nv.wg_partial_sum(partial, slots, (DW_KERNEL + 1) * D, small[:(DW_KERNEL + 1) * D])
+            gv[pre + 'dwconv.weight'].view(D, DW_KERNEL).copy_(small[:DW_KERNEL * D].view(DW_KERNEL, D).t())
+            gv[pre + 'dwconv.bias'].copy_(small[DW_KERNEL * D:(DW_KERNEL + 1) * D])
+        nv.vc_ln_bwd(sv['e'], None, None, pk['norm'][0], LN_EPS, rowb0, da, db, partial)
+        norm_grads('backbone.norm')
+        # embed: its 7 taps are 7 shifted row slices of the zero-haloed mel image
+        d_e, mel_cl = db, sv['mel_cl']
+        g_in = r['g_in'][:D * EMBED_KERNEL * ce].view(D, EMBED_KERNEL * ce)
+        for tap in range(EMBED_KERNEL):
+            _wgrad(g_in[:, tap * ce:(tap + 1) * ce], d_e[HALO:P - HALO], mel_cl[tap:P - 2 * HALO + tap], prec, wpart)
+        gv['backbone.embed.weight'].copy_(g_in.view(D, EMBED_KERNEL, ce)[:, :, :nm].permute(0, 2, 1))
+        nv.colsum(d_e, ws64, gv['backbone.embed.bias'])
+        if want_mel:
+            d_mel_cl = r['d_mel_cl'][:P * ce].view(P, ce)
+            rows = r['d_mel_rows'][:B * N * ce].view(B * N, ce)
+            nv.hg_conv(d_e, pt['embed'], None, EMBED_KERNEL, 1, None, None, d_mel_cl, 1.0, False, rowb0, 1, prec)
+            torch.index_select(d_mel_cl, 0, self._mel_rows(sv['lens'], N, dev), out=rows)     # row 0 is a halo row: zero
+            gv['mel'].copy_(rows.view(B, N, ce)[:, :, :nm].transpose(1, 2))
+        return gv
+
+    def _mel_rows(self, lens, N, dev):
+        """(B N) int64: the packed row of frame n of utterance b, row 0 (a halo row) beyond its frames."""
+        key = ('mel_rows', tuple(lens), N, str(dev))
+        if getattr(self, '_mel_rows_cache', None) is None or self._mel_rows_cache[0] != key:
+            offs = self.packed_plan(lens)[3]
+            idx = torch.zeros(len(lens), N, dtype=torch.int64)
+            for b, (o, n) in enumerate(zip(offs, lens)):
+                idx[b, :n] = torch.arange(o, o + n)
+            self._mel_rows_cache = (key, idx.view(-1).to(dev))
+        return self._mel_rows_cache[1]
+
+
+class _Generate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vc, mel, lengths, *params):
+        out, sv = vc._generate_forward(mel, lengths)
+        ctx.vc, ctx.sv = vc, sv
+        ctx.names = [n for n, _ in vc.named_parameters()]
+        return out
+
+    @staticmethod
+    def backward(ctx, d_audio):
+        if ctx.sv is None:
+            raise RuntimeError("Vocos.generate: backward was already run; the kept state is freed by the first one")
+        want_mel = ctx.needs_input_grad[1]
+        gv = ctx.vc._backward(ctx.sv, d_audio, want_mel)
+        mel_dtype = ctx.sv['mel_dtype']
+        ctx.sv = None
+        return (None, gv['mel'].to(mel_dtype) if want_mel else None, None) + \
+            tuple(gv[n] if need else None for n, need in zip(ctx.names, ctx.needs_input_grad[3:]))
 
 
 def load_vocos(src, precision=None, hop_length=None, padding=None):

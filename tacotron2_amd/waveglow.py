@@ -39,7 +39,7 @@ from torch import nn
 
 from . import native as nv
 from .audio import STFT
-from .vocoder import PRECISIONS, Vocoder, checkpoint_source, host_lengths, packed_rows
+from .vocoder import PRECISIONS, Vocoder, checkpoint_source, host_lengths, packed_rows, _splitk, _wgrad
 
 HOP = 256                    # upsample stride (NVIDIA's ConvTranspose1d(n_mel, n_mel, 1024, stride=256))
 UP_KERNEL = 1024
@@ -830,25 +830,6 @@ def _nll_sums(z, log_s, rows):
     out = buf[B * nchunk * 2:].view(B, 2)
     nv.wg_nll(z, log_s, rows, buf[:B * nchunk * 2], out)
     return out
-
-
-def _splitk(M, N, K):
-    """Split count of a weight-gradient product [M][N] over K rows: about two workgroups of 128 x 128 per compute unit,
-    at least 512 rows per slice."""
-    tiles = -(-M // 128) * -(-N // 128)
-    return max(1, min(-(-512 // tiles), K // 512, 64))
-
-
-def _wgrad(out, A, Bm, prec, partials):
-    """out [M][N] = A^T . Bm over the rows of A [K][M] and Bm [K][N] (halo rows are zero in one of them), split-K in a
-    fixed order."""
-    K, M = A.shape
-    s = _splitk(M, Bm.shape[1], K)
-    if s == 1:
-        nv.gemm(out, A, Bm, a_km=True, b_kn=True, fast=prec)
-    else:
-        nv.gemm(out, A, Bm, a_km=True, b_kn=True, splitk=s, partials=partials, fast=prec)
-        nv.splitk_reduce2d(partials, s, out)
 
 
 class _SavedState:
