@@ -908,6 +908,37 @@ int t2amd_mel_log_compress_f32(const float* mel, long long ld, float* out, int B
                                float clip, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Mel front end, backward (csrc/audio_bwd.hip): the row passes between the two products of the way back,
+ *   d_mag[R][Fpad] = d_mel[R][n_mel] . mel_basis and d_frames[R][L] = d_spec[R][Kp] . forward_basis
+ * (t2amd_gemm_f32, precision 0 or 1), and a masked L1 loss on the log-mels.  The reference has no counterpart
+ * (torch autograd differentiates layers.py:63-80 there).  No atomics: two calls give the same bits.
+ * ------------------------------------------------------------------------------------ */
+/* d_mel[(b*n + j)*ldd + m] = d_out[b][m][j] / mel[(b*n + j)*ld + m] where mel >= clip (the gradient passes at equality, torch's
+ * clamp(min=) rule), exactly 0 elsewhere: t2amd_mel_log_compress_f32's gradient with its transpose undone. */
+int t2amd_mel_log_bwd_f32(const float* d_out, const float* mel, long long ld, float* d_mel, long long ldd, int B, int n,
+                          int n_mel, float clip, void* stream);
+/* d_spec[r] = [d_mag re / mag (F) | d_mag im / mag (F) | 0 (Kp - 2F)] from spec[r] = [re (F) | im (F)]; mag is recomputed as
+ * t2amd_stft_magnitude_f32 computes it; both gradients are exactly 0 where mag == 0 (a definition; torch's sqrt gives NaN). */
+int t2amd_stft_magnitude_bwd_f32(const float* d_mag, long long ldm, const float* spec, long long lds, float* d_spec,
+                                 long long ldd, long long rows, int F, int Kp, void* stream);
+/* d_y[b][t] = the sum, in ascending padded position and ascending frame order, of d_frames[b*n + j][q - j*hop] over the padded
+ * positions q that t2amd_reflect_index maps onto t (pad - t, pad + t, pad + 2(T-1) - t) and the frames j < n = T/hop + 1 that
+ * cover q: the gradient of the strided frame view of t2amd_reflect_pad_f32's output, without a padded buffer. */
+int t2amd_stft_frames_fold_f32(const float* d_frames, long long ldf, long long f_floats, float* d_y, long long ldy,
+                               long long y_floats, int B, int T, int n, int L, int hop, int pad, void* stream);
+/* (b, m) rows of n frames per partial slot of t2amd_mel_l1_fwd_f32. */
+int t2amd_mel_l1_rows_per_slot(int n);
+/* partial[s] = (sum over slot s's rows (b, m) and frames i < lens[b] of |out[b][m][i] - target[b][m][i]|) / count; out (B, n_mel, n),
+ * target (B, n_mel, N), N <= n, lens NULL: N frames each; count = n_mel * sum(lens).  t2amd_wg_partial_sum_f32 over the
+ * ceil(B n_mel / rows_per_slot) slots gives the loss. */
+int t2amd_mel_l1_fwd_f32(const float* out, const float* target, const int* lens, int B, int n_mel, int n, int N,
+                         long long count, float* partial, long long partial_floats, void* stream);
+/* d_out[b][m][j] = sign(out - target) g[0] / count for j < lens[b], exactly 0 for the other j < n; g: the upstream scalar on the
+ * device. */
+int t2amd_mel_l1_bwd_f32(const float* out, const float* target, const int* lens, const float* g, int B, int n_mel, int n,
+                         int N, long long count, float* d_out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
  * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are
  * t2amd_gemm_f32 calls (precision 0 exact f32 or 1 split-bf16):

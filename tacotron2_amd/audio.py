@@ -35,6 +35,14 @@ log-mels.  One iteration on the whole batch is four launches on one stream (csrc
 Ragged batches run in one packed frame space (utterance b owns n_b + ceil(L/hop) - 1 consecutive rows), so the GEMMs
 cover sum(n_b + 3) rows at L = 1024, hop = 256, not B * n_max.  The mel inversion is the clamped pseudo-inverse
 max(pinv(mel_basis) . exp(mel), 0) (the reference gives no recipe).
+
+The way back (csrc/audio_bwd.hip): ``mel_spectrogram`` of a signal that requires grad returns the same
+bits with a ``grad_fn``; it keeps the spectrum and the mel rows and its backward is five launches (log-compress backward,
+d_mag = d_mel . mel_basis, magnitude backward, d_frames = d_spec . forward_basis, overlap-add with the reflect fold).
+``MelLoss(stft)(audio, target_mel, lengths)`` is the masked mean |log-mel(audio) - target| as one autograd function from the
+samples to the scalar: the term a vocoder is fine-tuned on (``tacotron2_amd.vocos_train``).  Two subgradients are definitions:
+the clamp passes the gradient where mel >= clip (torch's rule), and a bin of magnitude exactly 0 gets gradient 0 (torch's
+sqrt gives NaN there).
 """
 import os
 
@@ -178,6 +186,7 @@ class STFT(torch.nn.Module):
         basis = torch.from_numpy(fourier_basis(filter_length, win_length, window))
         self.register_buffer('forward_basis', basis[:, None, :].contiguous())      # (2F, 1, L) like the reference
         self._gl_tables = {}            # per device: interleaved bases, squared window (plain attributes, not buffers)
+        self._bwd_tables = {}           # per device: the transposed basis of the backward pass
 
     def gl_tables(self, device):
         """Device tables of the inverse / Griffin-Lim path, built on first use: ``fbi`` (2F, L) forward basis with re/im
@@ -200,8 +209,28 @@ class STFT(torch.nn.Module):
             self._gl_tables[device] = t
         return t
 
+    def bwd_tables(self, device):
+        """Device table of the backward of the forward transform, built on first use (a plain attribute like ``gl_tables``):
+        ``fbt`` (L, Kp) = forward_basis transposed, Kp = 2F rounded up to the 32-deep k-steps of the split-bf16 GEMM, zero
+        columns beyond 2F (the B operand of d_frames = d_spec . forward_basis)."""
+        device = torch.device(device)
+        t = self._bwd_tables.get(device)
+        if t is None:
+            L, F = self.filter_length, self.cutoff
+            Kp = (2 * F + 31) // 32 * 32
+            fbt = torch.zeros(L, Kp, dtype=torch.float32, device=device)
+            fbt[:, :2 * F] = self.forward_basis.view(2 * F, L).to(device).t()
+            t = {"fbt": fbt, "Kp": Kp}
+            self._bwd_tables[device] = t
+        return t
+
     def magnitude_rows(self, y):
         """y (B, T) device f32 -> (mag (B*n, Fpad) with zero columns beyond F, n)."""
+        mag, _, n = self._magnitude_spec_rows(y)
+        return mag, n
+
+    def _magnitude_spec_rows(self, y):
+        """``magnitude_rows`` with the spectrum it came from: (mag, spec (B*n, 2F) rows [re | im], n)."""
         B, T = y.shape
         L, hop, F = self.filter_length, self.hop_length, self.cutoff
         if T <= L // 2:
@@ -216,7 +245,7 @@ class STFT(torch.nn.Module):
         Fpad = (F + 15) // 16 * 16
         mag = torch.empty(B * n, Fpad, dtype=torch.float32, device=y.device)
         nv.stft_magnitude(spec, mag, F)
-        return mag, n
+        return mag, spec, n
 
     def transform_magnitude(self, y):
         """(B, F, n) magnitudes, the first return value of the reference's ``transform``."""
@@ -381,6 +410,7 @@ class TacotronSTFT(torch.nn.Module):
         padded[:, :F] = self.mel_basis
         self.register_buffer('_mel_basis_padded', padded, persistent=False)
         self._mel_pinv = {}             # per device, built on first use by mel_to_magnitude (not a buffer)
+        self._mel_basis_t = {}          # per device, built on first use by the backward pass (not a buffer)
         self.clip_val = 1e-5
         if torch.cuda.is_available():
             self.cuda()
@@ -437,20 +467,175 @@ class TacotronSTFT(torch.nn.Module):
         mag = self.mel_to_magnitude(mel, lengths)
         return griffin_lim(mag, self.stft_fn, n_iters=n_iters, angles=angles, lengths=lengths, precision=precision)
 
-    def mel_spectrogram(self, y, check_range=True):
-        """y (B, T) float in [-1, 1] -> (B, n_mel_channels, T // hop + 1) on the GPU."""
-        y = _device_signal(y, self.mel_basis)
-        if check_range and not nv.validate_only():
-            lo, hi = (float(v) for v in torch.stack(torch.aminmax(y)).tolist())
-            if lo < -1.0 or hi > 1.0:
-                raise AssertionError("samples must lie in [-1, 1] (got [%g, %g]); divide by max_wav_value" % (lo, hi))
-        mag, n = self.stft_fn.magnitude_rows(y)
+    def mel_basis_t(self, device):
+        """(Fpad, n_mel) float32: the zero-padded filterbank transposed, the B operand of d_mag = d_mel . mel_basis; built on
+        first use (not a buffer)."""
+        device = torch.device(device)
+        t = self._mel_basis_t.get(device)
+        if t is None:
+            t = self._mel_basis_padded.to(device).t().contiguous()
+            self._mel_basis_t[device] = t
+        return t
+
+    def _check_range(self, y):
+        lo, hi = (float(v) for v in torch.stack(torch.aminmax(y)).tolist())
+        if lo < -1.0 or hi > 1.0:
+            raise AssertionError("samples must lie in [-1, 1] (got [%g, %g]); divide by max_wav_value" % (lo, hi))
+
+    def _mel_forward(self, y):
+        """The launches of ``mel_spectrogram`` on device samples y (B, T) -> (log-mels, spec rows, mel rows)."""
+        mag, spec, n = self.stft_fn._magnitude_spec_rows(y)
         B = y.shape[0]
         mel_rows = torch.empty(B * n, self.n_mel_channels, dtype=torch.float32, device=y.device)
         nv.gemm(mel_rows, mag, self._mel_basis_padded)
         out = torch.empty(B, self.n_mel_channels, n, dtype=torch.float32, device=y.device)
         nv.mel_log_compress(mel_rows, out, self.clip_val)
+        return out, spec, mel_rows
+
+    def kept_state_floats(self, B, T):
+        """Floats kept between the forward and the backward of ``mel_spectrogram`` / ``MelLoss`` for (B, T) samples: the
+        spectrum (B n, 2F) and the mel rows (B n, n_mel)."""
+        n = T // self.stft_fn.hop_length + 1
+        return B * n * (2 * self.stft_fn.cutoff + self.n_mel_channels)
+
+    def _mel_backward(self, d_out, spec, mel_rows, B, T, fast):
+        """d_y (B, T) float32 from d_out (B, n_mel, n) and the kept spectrum and mel rows: five launches."""
+        st = self.stft_fn
+        L, hop, F = st.filter_length, st.hop_length, st.cutoff
+        dev, R = spec.device, spec.shape[0]
+        f32 = dict(dtype=torch.float32, device=dev)
+        tab = st.bwd_tables(dev)
+        d_mel = torch.empty(R, self.n_mel_channels, **f32)
+        nv.mel_log_bwd(d_out, mel_rows, d_mel, self.clip_val)
+        d_mag = torch.empty(R, (F + 15) // 16 * 16, **f32)
+        nv.gemm(d_mag, d_mel, self.mel_basis_t(dev), fast=fast)
+        d_spec = torch.empty(R, tab["Kp"], **f32)
+        nv.stft_magnitude_bwd(d_mag, spec, d_spec, F)
+        d_frames = torch.empty(R, L, **f32)
+        nv.gemm(d_frames, d_spec, tab["fbt"], fast=fast)
+        d_y = torch.empty(B, T, **f32)
+        nv.stft_frames_fold(d_frames, d_y, hop, L // 2)
+        return d_y
+
+    def mel_spectrogram(self, y, check_range=True, precision='fp32'):
+        """y (B, T) float in [-1, 1] -> (B, n_mel_channels, T // hop + 1) on the GPU.
+
+        When gradients are enabled and ``y.requires_grad`` the result carries a ``grad_fn`` (the same launches, so the same
+        bits): it keeps the spectrum and the mel rows (``kept_state_floats``) and ``backward()`` gives ``y`` a float32
+        gradient of its shape.  ``precision`` ('fp32' or 'bf16x3') selects the two products of the backward only.  Two
+        subgradients are definitions: the gradient passes where mel >= clip_val (torch's clamp rule), and a bin whose
+        magnitude is exactly 0 gets gradient 0, where torch's sqrt gives NaN.  The range check costs a host
+        synchronisation: training callers pass ``check_range=False``."""
+        if precision not in _PRECISIONS:
+            raise ValueError("precision must be one of %s, got %r" % (sorted(_PRECISIONS), precision))
+        if torch.is_grad_enabled() and torch.is_tensor(y) and y.requires_grad:
+            return _MelSpectrogram.apply(self, y, check_range, precision)
+        y = _device_signal(y, self.mel_basis)
+        if check_range and not nv.validate_only():
+            self._check_range(y)
+        return self._mel_forward(y)[0]
+
+
+class _MelSpectrogram(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, stft, y, check_range, precision):
+        ys = _device_signal(y, stft.mel_basis)
+        if check_range and not nv.validate_only():
+            stft._check_range(ys)
+        out, spec, mel_rows = stft._mel_forward(ys)
+        ctx.stft, ctx.kept, ctx.fast = stft, (spec, mel_rows), _PRECISIONS[precision]
+        ctx.y_shape, ctx.y_device = tuple(ys.shape), y.device
         return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        if ctx.kept is None:
+            raise RuntimeError("mel_spectrogram: backward was already run; the kept state is freed by the first one")
+        spec, mel_rows = ctx.kept
+        ctx.kept = None
+        d_out = d_out.to(device=spec.device, dtype=torch.float32).contiguous()
+        d_y = ctx.stft._mel_backward(d_out, spec, mel_rows, ctx.y_shape[0], ctx.y_shape[1], ctx.fast)
+        return None, d_y.to(ctx.y_device), None, None
+
+
+class MelLoss(torch.nn.Module):
+    """Masked mean absolute error between the log-mels of ``audio`` and ``target_mel``:
+
+        loss = sum_{b, m, i < lengths_b} |mel_spectrogram(audio)[b, m, i] - target_mel[b, m, i]| / (n_mel sum_b lengths_b)
+
+    ``MelLoss(stft)(audio, target_mel, lengths=None, precision='fp32')`` -> a scalar on the GPU.  ``audio`` is (B, T) or
+    (B, 1, T) in [-1, 1] (not checked: the check would cost a host synchronisation per step), ``target_mel`` (B, n_mel, N)
+    with N <= T // hop + 1, ``lengths`` the frames of every utterance (default N).  One autograd function from the samples to
+    the scalar; it keeps the spectrum, the mel rows and the target.  ``precision`` as in ``mel_spectrogram``."""
+
+    def __init__(self, stft):
+        super().__init__()
+        if not isinstance(stft, TacotronSTFT):
+            raise TypeError("MelLoss needs a tacotron2_amd.audio.TacotronSTFT")
+        self.stft = stft
+
+    def forward(self, audio, target_mel, lengths=None, precision='fp32'):
+        st = self.stft
+        if precision not in _PRECISIONS:
+            raise ValueError("precision must be one of %s, got %r" % (sorted(_PRECISIONS), precision))
+        if audio.dim() == 3 and audio.shape[1] == 1:
+            audio = audio.reshape(audio.shape[0], audio.shape[2])
+        if audio.dim() != 2:
+            raise ValueError("MelLoss: expected (B, T) or (B, 1, T) samples, got shape %s" % (tuple(audio.shape),))
+        B, T = audio.shape
+        if target_mel.dim() != 3 or target_mel.shape[0] != B or target_mel.shape[1] != st.n_mel_channels:
+            raise ValueError("MelLoss: expected (%d, %d, N) target log-mels, got shape %s"
+                             % (B, st.n_mel_channels, tuple(target_mel.shape)))
+        n, N = T // st.stft_fn.hop_length + 1, target_mel.shape[2]
+        if N < 1 or N > n:
+            raise ValueError("MelLoss: the target has %d frames, %d samples give %d" % (N, T, n))
+        lens = None
+        if lengths is not None:
+            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+            if len(lens) != B:
+                raise ValueError("MelLoss: %d lengths for a batch of %d" % (len(lens), B))
+            if min(lens) < 1 or max(lens) > N:
+                raise ValueError("MelLoss: lengths must lie in [1, %d], got %s" % (N, lens))
+        if not st.mel_basis.is_cuda and not nv.validate_only():
+            raise nv.NativeError("tacotron2_amd.audio: move the module to the MI355X first (.cuda()); there is no CPU path")
+        return _MelLoss.apply(st, audio, target_mel, lens, precision)
+
+
+class _MelLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, stft, audio, target, lens, precision):
+        y = _device_signal(audio, stft.mel_basis)
+        dev = y.device
+        out, spec, mel_rows = stft._mel_forward(y)
+        B, n_mel, n = out.shape
+        tgt = target.detach().to(device=dev, dtype=torch.float32).contiguous()
+        lens_dev = None if lens is None else torch.tensor(lens, dtype=torch.int32).to(dev)
+        count = n_mel * (sum(lens) if lens is not None else B * tgt.shape[2])
+        slots = nv.mel_l1_slots(B, n_mel, n)
+        partial = torch.empty(slots, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        nv.mel_l1_fwd(out, tgt, lens_dev, count, partial)
+        nv.wg_partial_sum(partial, slots, 1, loss)
+        ctx.stft, ctx.kept, ctx.fast = stft, (spec, mel_rows, tgt, lens_dev), _PRECISIONS[precision]
+        ctx.count, ctx.y_shape, ctx.y_device = count, tuple(y.shape), audio.device
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.kept is None:
+            raise RuntimeError("MelLoss: backward was already run; the kept state is freed by the first one")
+        spec, mel_rows, tgt, lens_dev = ctx.kept
+        ctx.kept = None
+        stft, (B, T) = ctx.stft, ctx.y_shape
+        dev = spec.device
+        n = spec.shape[0] // B
+        g = g.to(device=dev, dtype=torch.float32).reshape(1).contiguous()
+        out = torch.empty(B, stft.n_mel_channels, n, dtype=torch.float32, device=dev)
+        nv.mel_log_compress(mel_rows, out, stft.clip_val)            # the forward's bits again, rather than kept
+        d_out = torch.empty_like(out)
+        nv.mel_l1_bwd(out, tgt, lens_dev, g, ctx.count, d_out)
+        d_y = stft._mel_backward(d_out, spec, mel_rows, B, T, ctx.fast)
+        return None, d_y.to(ctx.y_device), None, None, None
 
 
 def precompute_mels(filelist, hparams, out_dir, out_filelist=None):

@@ -10,14 +10,7 @@
 //   reflect pad (T -> T + L samples), magnitude (2F -> F, zero-filled to the padded row), log-compress + transpose.
 #include "common.h"
 
-// index into y[0..T) of padded sample i (i already shifted by -pad): torch 'reflect' (edge sample not repeated)
-static __host__ __device__ __forceinline__ long long t2_reflect(long long i, long long T) {
-    if (i < 0) i = -i;
-    if (i >= T) i = 2 * (T - 1) - i;
-    return i;
-}
-
-// host-visible copy of the index rule, for the CPU unit test of the padding arithmetic
+// host-visible copy of the index rule (t2_reflect, common.h), for the CPU unit test of the padding arithmetic
 extern "C" long long t2amd_reflect_index(long long i, long long T) { return t2_reflect(i, T); }
 
 __global__ void __launch_bounds__(256) reflect_pad_kernel(const float* __restrict__ y, long long ldy,

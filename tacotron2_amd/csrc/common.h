@@ -196,5 +196,13 @@ int t2amd_check_lstm_bwd_(const t2amd_lstm_bwd* a);      // rnn.hip: argument ch
 static inline bool t2_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int t2_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// index into y[0..T) of padded sample i (i already shifted by -pad): torch 'reflect' (edge sample not repeated).  The one
+// statement of the mirror rule: the forward pad (audio.hip) and the gradient's fold (audio_bwd.hip) both call it.
+static __host__ __device__ __forceinline__ long long t2_reflect(long long i, long long T) {
+    if (i < 0) i = -i;
+    if (i >= T) i = 2 * (T - 1) - i;
+    return i;
+}
+
 // The most rows of a packed row image (HiFi-GAN, Vocos): 2^31 - 256, so that grid.x = rows / 128 and 32-bit row sums hold
 #define T2_MAX_ROWS 2147483392LL

@@ -16,7 +16,8 @@ Per call: one mel-packing launch, conv_pre, per stage one transposed-convolution
 resblock convolution (t2amd_hg_conv_f32: the leaky-ReLU on the operand, the residual and the multi-receptive-field sum in
 the epilogue), conv_post with tanh.  One workspace allocation per call; the stage loop does no allocation, copy or host
 synchronisation and has no loop over utterances.  Channel counts below 32 (V2's last stages) run zero-padded to 32.
-Training the generator and its discriminators is out of scope.  The arithmetic is restated in float64 torch by
+Training the generator and its discriminators is out of scope; the mel-reconstruction term of its objective exists on its
+own (``tacotron2_amd.audio.MelLoss``), but the generator has no backward pass to feed it into.  The arithmetic is restated in float64 torch by
 tests/hifigan_ref.py; DESIGN.md section 11 has the layout.
 """
 import numpy as np

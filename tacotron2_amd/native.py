@@ -285,6 +285,8 @@ SYMBOLS = [
     "t2amd_lstm_seq_batch_persistent_flag_bytes", "t2amd_lstm_seq_batch_persistent_supported", "t2amd_lstm_seq_fwd2_batch_persistent_f32", "t2amd_encoder_handoff_timeouts",
     "t2amd_lstm_seq_bwd2_batch_persistent_supported", "t2amd_lstm_seq_bwd2_batch_persistent_f32",
     "t2amd_reflect_pad_f32", "t2amd_reflect_index", "t2amd_stft_magnitude_f32", "t2amd_mel_log_compress_f32",
+    "t2amd_mel_log_bwd_f32", "t2amd_stft_magnitude_bwd_f32", "t2amd_stft_frames_fold_f32", "t2amd_mel_l1_rows_per_slot",
+    "t2amd_mel_l1_fwd_f32", "t2amd_mel_l1_bwd_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
@@ -389,6 +391,12 @@ def _argtypes():
         "t2amd_reflect_pad_f32": [_P, _L, _P, _L, _I, _I, _I, _I, _P],
         "t2amd_stft_magnitude_f32": [_P, _L, _P, _L, _L, _I, _I, _P],
         "t2amd_mel_log_compress_f32": [_P, _L, _P, _I, _I, _I, _F, _P],
+        "t2amd_mel_log_bwd_f32": [_P, _P, _L, _P, _L, _I, _I, _I, _F, _P],
+        "t2amd_stft_magnitude_bwd_f32": [_P, _L, _P, _L, _P, _L, _L, _I, _I, _P],
+        "t2amd_stft_frames_fold_f32": [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P],
+        "t2amd_mel_l1_rows_per_slot": [_I],
+        "t2amd_mel_l1_fwd_f32": [_P, _P, _P, _I, _I, _I, _I, _L, _P, _L, _P],
+        "t2amd_mel_l1_bwd_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _L, _P, _P],
         "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
         "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
@@ -1636,6 +1644,76 @@ def mel_log_compress(mel, out, clip):
         raise NativeError("mel_log_compress: shape mismatch mel=%s out=%s" % (tuple(mel.shape), tuple(out.shape)))
     _check(load().t2amd_mel_log_compress_f32(pm, _i64(ld), ptr(_fullc(out)), B, n, n_mel, C.c_float(clip), _stream()),
            "t2amd_mel_log_compress_f32")
+
+
+# ---- the way back and the mel L1 loss (csrc/audio_bwd.hip) ---------------------------------------------------------------
+def mel_log_bwd(d_out, mel, d_mel, clip):
+    """d_mel (B*n, n_mel) = d_out (B, n_mel, n) transposed per utterance / mel where mel >= clip, 0 elsewhere."""
+    pm, ld, R, n_mel = _mat(mel)
+    pd, ldd, Rd, n_mel_d = _mat(d_mel)
+    if d_out.dim() != 3 or (Rd, n_mel_d) != (R, n_mel) or d_out.shape[1] != n_mel or d_out.shape[0] * d_out.shape[2] != R:
+        raise NativeError("mel_log_bwd: shape mismatch d_out=%s mel=%s d_mel=%s" % (tuple(d_out.shape), tuple(mel.shape),
+                                                                                  tuple(d_mel.shape)))
+    B, _, n = d_out.shape
+    _check(load().t2amd_mel_log_bwd_f32(ptr(_fullc(d_out)), pm, _i64(ld), pd, _i64(ldd), B, n, n_mel, C.c_float(clip), _stream()),
+           "t2amd_mel_log_bwd_f32")
+
+
+def stft_magnitude_bwd(d_mag, spec, d_spec, F):
+    """d_spec[r] = [d_mag re / mag | d_mag im / mag | 0] from spec[r] = [re (F) | im (F)]; 0 where mag == 0."""
+    pg, ldm, R, Fm = _mat(d_mag)
+    ps, lds, Rs, C2 = _mat(spec)
+    pd, ldd, Rd, Kp = _mat(d_spec)
+    if (Rs, Rd) != (R, R) or C2 < 2 * F or Fm < F or Kp < 2 * F:
+        raise NativeError("stft_magnitude_bwd: shape mismatch d_mag=%s spec=%s d_spec=%s F=%d"
+                          % (tuple(d_mag.shape), tuple(spec.shape), tuple(d_spec.shape), F))
+    _check(load().t2amd_stft_magnitude_bwd_f32(pg, _i64(ldm), ps, _i64(lds), pd, _i64(ldd), _i64(R), int(F), int(Kp), _stream()),
+           "t2amd_stft_magnitude_bwd_f32")
+
+
+def stft_frames_fold(d_frames, d_y, hop, pad):
+    """d_y (B, T) = the overlap-add of the frame gradients d_frames (B*n, L), n = T // hop + 1, folded back through the reflect
+    padding of `pad` samples."""
+    pf, ldf, R, L = _mat(d_frames)
+    py, ldy, B, T = _mat(d_y)
+    n = T // int(hop) + 1
+    if R != B * n:
+        raise NativeError("stft_frames_fold: %d frame rows for (B, T) = %s at hop %d (%d frames each)" % (R, tuple(d_y.shape), hop, n))
+    _check(load().t2amd_stft_frames_fold_f32(pf, _i64(ldf), _i64(_floats(d_frames)), py, _i64(ldy), _i64(_floats(d_y)), B, T, n, L,
+                                             int(hop), int(pad), _stream()), "t2amd_stft_frames_fold_f32")
+
+
+def mel_l1_slots(B, n_mel, n):
+    """Partial slots of ``mel_l1_fwd`` for (B, n_mel, n) log-mels."""
+    return -(-int(B) * int(n_mel) // int(load().t2amd_mel_l1_rows_per_slot(int(n))))
+
+
+def _l1_args(who, out, target, lens):
+    if out.dim() != 3 or target.dim() != 3 or tuple(target.shape[:2]) != tuple(out.shape[:2]):
+        raise NativeError("%s: shape mismatch out=%s target=%s" % (who, tuple(out.shape), tuple(target.shape)))
+    B, n_mel, n = out.shape
+    if lens is not None and (lens.dtype != torch.int32 or lens.dim() != 1 or lens.numel() != B or not lens.is_contiguous()):
+        raise NativeError("%s: lens must be a contiguous int32 vector of %d frame counts" % (who, B))
+    return B, n_mel, n, target.shape[2]
+
+
+def mel_l1_fwd(out, target, lens, count, partial):
+    """partial[s] = slot s's share of sum |out - target| / count over the frames i < lens[b] (lens None: all N); out
+    (B, n_mel, n), target (B, n_mel, N).  ``wg_partial_sum`` over ``mel_l1_slots`` slots gives the loss."""
+    B, n_mel, n, N = _l1_args("mel_l1_fwd", out, target, lens)
+    _check(load().t2amd_mel_l1_fwd_f32(ptr(_fullc(out)), ptr(_fullc(target)), None if lens is None else ptr(lens, torch.int32), B,
+                                       n_mel, n, N, _i64(int(count)), ptr(_fullc(partial)), _i64(partial.numel()), _stream()),
+           "t2amd_mel_l1_fwd_f32")
+
+
+def mel_l1_bwd(out, target, lens, g, count, d_out):
+    """d_out (B, n_mel, n) = sign(out - target) g / count inside the mask, 0 outside; g: a one-element device tensor."""
+    B, n_mel, n, N = _l1_args("mel_l1_bwd", out, target, lens)
+    if tuple(d_out.shape) != tuple(out.shape) or g.numel() != 1:
+        raise NativeError("mel_l1_bwd: d_out %s beside out %s, g of %d elements" % (tuple(d_out.shape), tuple(out.shape), g.numel()))
+    _check(load().t2amd_mel_l1_bwd_f32(ptr(_fullc(out)), ptr(_fullc(target)), None if lens is None else ptr(lens, torch.int32),
+                                       ptr(_fullc(g)), B, n_mel, n, N, _i64(int(count)), ptr(_fullc(d_out)), _stream()),
+           "t2amd_mel_l1_bwd_f32")
 
 
 # ----------------------------------------------------------------------------

@@ -4,6 +4,8 @@
     audio = vc(mel)                                         # (B, 80, N) log-mels -> (B, 1, 256 N) float32
     audio = vc.infer(mel, lengths=frames)                   # ragged: every utterance as if alone, zero beyond hop n_b
     audio = vc.generate(mel); loss(audio).backward()        # infer's bits with a grad_fn: gradients of every parameter (and mel)
+    MelLoss(stft)(vc.generate(mel), mel).backward()         # the mel-reconstruction loss (tacotron2_amd.audio); a driver around
+                                                            # this step is tacotron2_amd.vocos_train
 
 A ConvNeXt stack on D-channel frame rows, one linear head that predicts log-magnitude and phase, one inverse STFT: nothing
 runs at the sample rate before the overlap-add.  The module keeps the published names (``backbone.embed``, ``backbone.norm``,
