@@ -24,22 +24,14 @@ would have seen.  One line per iteration, ``"{iteration}:\\t{loss:.9f}"``; the l
 enqueued, and ``MelLoss`` runs without a range check of the generated samples (it would cost a host synchronisation).
 There is no CPU compute path: without an MI355X the driver raises.
 """
-import argparse
-import copy
-import json
-import os
-
 import torch
 
-from . import native
+from . import vocoder_train as vtr
 from .audio import MelLoss
-from .distributed import apply_gradient_allreduce, reduce_tensor
-from .mel2samp import Mel2Samp
-from .optim import FusedAdam
 from .vocoder import PRECISIONS
 from .vocos import Vocos, load_vocos
-from .waveglow_train import _paths, _value, epoch_batches, init_distributed
 
+WHO = 'vocos_train'
 DEFAULTS = {
     'train_config': dict(precision='fp32', output_directory='checkpoints', epochs=100000, learning_rate=2e-4,
                          iters_per_checkpoint=2000, batch_size=16, seed=1234, checkpoint_path='', with_tensorboard=False,
@@ -52,35 +44,9 @@ DEFAULTS = {
 }
 
 
-def _merge(dst, src, where):
-    for k, v in src.items():
-        if k not in dst:
-            raise KeyError("vocos_train: unknown configuration key %s%s" % (where, k))
-        if isinstance(dst[k], dict):
-            _merge(dst[k], v, where + k + '.')
-        else:
-            dst[k] = v
-
-
 def load_config(path=None, overrides=()):
     """The defaults, then the JSON file (any subset of the sections), then the ``key=value`` overrides."""
-    cfg = copy.deepcopy(DEFAULTS)
-    if path:
-        with open(path) as fh:
-            _merge(cfg, json.load(fh), '')
-    for item in overrides:
-        if '=' not in item:
-            raise ValueError("vocos_train: --set takes key=value, got %r" % item)
-        key, text = item.split('=', 1)
-        want = tuple(key.split('.'))
-        hits = [p for p in _paths(cfg) if p == want or (len(want) == 1 and p[-1] == want[0])]
-        if len(hits) != 1:
-            raise KeyError("vocos_train: configuration key %s %s" % (key, "is ambiguous: %s" % hits if hits else "does not exist"))
-        node = cfg
-        for k in hits[0][:-1]:
-            node = node[k]
-        node[hits[0][-1]] = _value(text)
-    return cfg
+    return vtr.load_config(DEFAULTS, WHO, path, overrides)
 
 
 def check_config(config):
@@ -111,13 +77,13 @@ def make_model(config):
     return model
 
 
+def _payload(model, optimizer, learning_rate, iteration, vocos_config):
+    return dict(state_dict=vtr.cpu_state(model), iteration=iteration, optimizer=optimizer.state_dict(),
+                learning_rate=learning_rate, vocos_config=vocos_config)
+
+
 def save_checkpoint(model, optimizer, learning_rate, iteration, vocos_config, filepath):
-    print("Saving model and optimizer state at iteration {} to {}".format(iteration, filepath))
-    payload = dict(state_dict={k: v.detach().cpu() for k, v in model.state_dict().items()}, iteration=iteration,
-                   optimizer=optimizer.state_dict(), learning_rate=learning_rate, vocos_config=vocos_config)
-    tmp = filepath + '.tmp'
-    torch.save(payload, tmp)
-    os.replace(tmp, filepath)
+    vtr.save_checkpoint(_payload(model, optimizer, learning_rate, iteration, vocos_config), filepath)
 
 
 def resume(checkpoint_path, optimizer):
@@ -142,67 +108,21 @@ def train_step(model, loss_fn, optimizer, mel, n_in, n_cmp, loss_precision):
 
 
 def train(num_gpus, rank, group_name, config):
-    t, data_config, dist_config = config['train_config'], config['data_config'], config['dist_config']
+    t = config['train_config']
     n_in, n_cmp = check_config(config)
-    if not torch.cuda.is_available() and not native.validate_only():
-        raise native.NativeError("vocos_train: no MI355X visible and the engine has no CPU path")
-    if num_gpus > 1:
-        rank, num_gpus = init_distributed(rank, num_gpus, group_name, **dist_config)
-    torch.manual_seed(t['seed'])
-    if torch.cuda.is_available():
-        torch.cuda.manual_seed(t['seed'])
-
-    model = make_model(config)
-    vocos_config = config['vocos_config']
-    if vocos_config['padding'] == 'center':
-        n_cmp = n_in                                              # hop (N - 1) samples: N frames, all compared
-    if torch.cuda.is_available():
-        model = model.cuda()
-    if num_gpus > 1:
-        model = apply_gradient_allreduce(model)
-    learning_rate = float(t['learning_rate'])
-    optimizer = FusedAdam(model.parameters(), lr=learning_rate)
-    iteration = 0
-    if t['checkpoint_path']:
-        iteration = resume(t['checkpoint_path'], optimizer) + 1       # the iteration after the saved one
-
-    trainset = Mel2Samp(seed=t['seed'], **data_config)
-    loss_fn = MelLoss(trainset_stft(trainset))
     loss_precision = 'fp32' if t['precision'] == 'fp32' else 'bf16x3'
-    per_epoch = len(epoch_batches(len(trainset), t['batch_size'], t['seed'], 0, rank, num_gpus))
-    if per_epoch == 0:
-        raise ValueError("vocos_train: %d recordings are less than one batch of %d on %d rank(s)"
-                         % (len(trainset), t['batch_size'], num_gpus))
-    if rank == 0 and not os.path.isdir(t['output_directory']):
-        os.makedirs(t['output_directory'])
-        os.chmod(t['output_directory'], 0o775)
-    logger = None
-    if t['with_tensorboard'] and rank == 0:
-        from torch.utils.tensorboard import SummaryWriter
-        logger = SummaryWriter(os.path.join(t['output_directory'], 'logs'))
 
-    model.train()
-    last = None
-    for epoch in range(iteration // per_epoch, t['epochs']):
-        print("Epoch: {}".format(epoch))
-        trainset.set_epoch(epoch)
-        batches = epoch_batches(len(trainset), t['batch_size'], t['seed'], epoch, rank, num_gpus)
-        for idx in batches[iteration % per_epoch if epoch == iteration // per_epoch else 0:]:
-            audio = trainset.collate([trainset[i] for i in idx])
-            mel = trainset.batch_mels(audio)
-            loss = train_step(model, loss_fn, optimizer, mel, n_in, n_cmp, loss_precision)
-            shown = reduce_tensor(loss, num_gpus) if num_gpus > 1 else loss
-            last = float(shown.item())
-            print("{}:\t{:.9f}".format(iteration, last), flush=True)
-            if logger is not None:
-                logger.add_scalar('training_loss', last, iteration)
-            if iteration % t['iters_per_checkpoint'] == 0 and rank == 0:
-                save_checkpoint(model, optimizer, learning_rate, iteration, vocos_config,
-                                os.path.join(t['output_directory'], "vocos_{}".format(iteration)))
-            iteration += 1
-            if t['max_iterations'] is not None and iteration > t['max_iterations']:
-                return iteration - 1, last
-    return iteration - 1, last
+    def make_step(model, optimizer, trainset, num_gpus):
+        loss_fn = MelLoss(trainset_stft(trainset))
+        # the geometry is the model's (a checkpoint's wins): 'center' returns hop (N - 1) samples, N frames, all compared
+        compared = n_in if config['vocos_config']['padding'] == 'center' else n_cmp
+        return lambda audio, mel: vtr.shown_loss(                 # all-reduced AFTER the optimizer's step
+            train_step(model, loss_fn, optimizer, mel, n_in, compared, loss_precision), num_gpus)
+
+    return vtr.train(
+        WHO, num_gpus, rank, group_name, config, make_step=make_step, make_model=lambda: make_model(config),
+        resume=lambda model, optimizer: resume(t['checkpoint_path'], optimizer),
+        checkpoint=lambda *state: (_payload(*state, config['vocos_config']), "vocos_{}"))
 
 
 def trainset_stft(trainset):
@@ -215,16 +135,7 @@ def trainset_stft(trainset):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('-c', '--config', type=str, default=None, help='JSON file with the configuration sections')
-    ap.add_argument('-r', '--rank', type=int, default=0, help='rank of this process')
-    ap.add_argument('-g', '--group_name', type=str, default='', help='name of the group of processes')
-    ap.add_argument('--n_gpus', type=int, default=None, help='number of ranks (default: WORLD_SIZE, else 1)')
-    ap.add_argument('--set', action='append', default=[], metavar='key=value', help='override a configuration key')
-    args = ap.parse_args(argv)
-    config = load_config(args.config, args.set)
-    num_gpus = args.n_gpus if args.n_gpus is not None else int(os.environ.get('WORLD_SIZE', 1))
-    return train(num_gpus, args.rank, args.group_name, config)
+    return vtr.main(WHO, __doc__, DEFAULTS, train, argv)
 
 
 if __name__ == '__main__':

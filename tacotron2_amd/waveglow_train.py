@@ -23,20 +23,15 @@ What is different from NVIDIA's driver:
   * the loss is read back once per iteration, after the whole step has been enqueued.
 There is no CPU compute path: without an MI355X the driver raises.
 """
-import argparse
-import copy
-import json
 import os
 
 import torch
-import torch.distributed as dist
 
-from . import native
-from .distributed import apply_gradient_allreduce, reduce_tensor
-from .mel2samp import Mel2Samp
-from .optim import FusedAdam
+from . import vocoder_train as vtr
+from .vocoder_train import epoch_batches, init_distributed  # noqa: F401  (this driver's surface)
 from .waveglow import PRECISIONS, WaveGlow
 
+WHO = 'waveglow_train'
 DEFAULTS = {
     'train_config': dict(fp16_run=False, precision=None, output_directory='checkpoints', epochs=100000, learning_rate=1e-4,
                          sigma=1.0, iters_per_checkpoint=2000, batch_size=12, seed=1234, checkpoint_path='',
@@ -49,50 +44,9 @@ DEFAULTS = {
 }
 
 
-def _merge(dst, src, where):
-    for k, v in src.items():
-        if k not in dst:
-            raise KeyError("waveglow_train: unknown configuration key %s%s" % (where, k))
-        if isinstance(dst[k], dict):
-            _merge(dst[k], v, where + k + '.')
-        else:
-            dst[k] = v
-
-
-def _paths(cfg, prefix=()):
-    for k, v in cfg.items():
-        if isinstance(v, dict):
-            yield from _paths(v, prefix + (k,))
-        else:
-            yield prefix + (k,)
-
-
-def _value(text):
-    try:
-        return json.loads(text)
-    except ValueError:
-        return {'true': True, 'false': False, 'none': None}.get(text.lower(), text)
-
-
 def load_config(path=None, overrides=()):
     """NVIDIA's defaults, then the JSON file (any subset of the sections), then the ``key=value`` overrides."""
-    cfg = copy.deepcopy(DEFAULTS)
-    if path:
-        with open(path) as fh:
-            _merge(cfg, json.load(fh), '')
-    for item in overrides:
-        if '=' not in item:
-            raise ValueError("waveglow_train: --set takes key=value, got %r" % item)
-        key, text = item.split('=', 1)
-        want = tuple(key.split('.'))
-        hits = [p for p in _paths(cfg) if p == want or (len(want) == 1 and p[-1] == want[0])]
-        if len(hits) != 1:
-            raise KeyError("waveglow_train: configuration key %s %s" % (key, "is ambiguous: %s" % hits if hits else "does not exist"))
-        node = cfg
-        for k in hits[0][:-1]:
-            node = node[k]
-        node[hits[0][-1]] = _value(text)
-    return cfg
+    return vtr.load_config(DEFAULTS, WHO, path, overrides)
 
 
 def precision_of(train_config):
@@ -104,29 +58,13 @@ def precision_of(train_config):
     return p
 
 
-def init_distributed(rank, num_gpus, group_name, dist_backend, dist_url):
-    """NVIDIA's ``init_distributed``: one process per GPU.  RANK / WORLD_SIZE in the environment (torch.distributed.run)
-    win over the flags."""
-    if 'RANK' in os.environ and 'WORLD_SIZE' in os.environ:
-        rank, num_gpus = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
-        dist_url = 'env://'
-        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
-    if not torch.cuda.is_available():
-        raise native.NativeError("waveglow_train: distributed mode requires an MI355X")
-    torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', rank)) % torch.cuda.device_count())
-    if not dist.is_initialized():
-        os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-        dist.init_process_group(dist_backend, init_method=dist_url, world_size=num_gpus, rank=rank)
-    return rank, num_gpus
+def _payload(model, optimizer, learning_rate, iteration, waveglow_config):
+    return dict(model=vtr.cpu_state(model), iteration=iteration, optimizer=optimizer.state_dict(),
+                learning_rate=learning_rate, waveglow_config=waveglow_config)
 
 
 def save_checkpoint(model, optimizer, learning_rate, iteration, waveglow_config, filepath):
-    print("Saving model and optimizer state at iteration {} to {}".format(iteration, filepath))
-    payload = dict(model={k: v.detach().cpu() for k, v in model.state_dict().items()}, iteration=iteration,
-                   optimizer=optimizer.state_dict(), learning_rate=learning_rate, waveglow_config=waveglow_config)
-    tmp = filepath + '.tmp'
-    torch.save(payload, tmp)
-    os.replace(tmp, filepath)
+    vtr.save_checkpoint(_payload(model, optimizer, learning_rate, iteration, waveglow_config), filepath)
 
 
 def load_checkpoint(checkpoint_path, model, optimizer):
@@ -144,88 +82,29 @@ def load_checkpoint(checkpoint_path, model, optimizer):
     return model, optimizer, int(ckpt.get('iteration', 0))
 
 
-def epoch_batches(n_items, batch_size, seed, epoch, rank=0, num_gpus=1):
-    """The index lists of this rank's batches of one epoch: a permutation seeded by (seed, epoch), dealt to the ranks in
-    turn (``DistributedSampler``'s rule), the incomplete last batch dropped."""
-    perm = torch.randperm(n_items, generator=torch.Generator().manual_seed(int(seed) + int(epoch))).tolist()
-    mine = perm[rank:n_items - n_items % num_gpus:num_gpus]
-    return [mine[i:i + batch_size] for i in range(0, len(mine) - batch_size + 1, batch_size)]
-
-
 def train(num_gpus, rank, group_name, config):
-    t, data_config, dist_config, waveglow_config = (config[k] for k in ('train_config', 'data_config', 'dist_config',
-                                                                         'waveglow_config'))
-    if not torch.cuda.is_available() and not native.validate_only():
-        raise native.NativeError("waveglow_train: no MI355X visible and the engine has no CPU path")
-    if num_gpus > 1:
-        rank, num_gpus = init_distributed(rank, num_gpus, group_name, **dist_config)
-    torch.manual_seed(t['seed'])
-    if torch.cuda.is_available():
-        torch.cuda.manual_seed(t['seed'])
+    t, waveglow_config = config['train_config'], config['waveglow_config']
+    sigma = float(t['sigma'])
 
-    model = WaveGlow(precision=precision_of(t), weight_norm=True, **waveglow_config)
-    if torch.cuda.is_available():
-        model = model.cuda()
-    if num_gpus > 1:
-        model = apply_gradient_allreduce(model)
-    learning_rate, sigma = float(t['learning_rate']), float(t['sigma'])
-    optimizer = FusedAdam(model.parameters(), lr=learning_rate)
-    iteration = 0
-    if t['checkpoint_path']:
-        model, optimizer, iteration = load_checkpoint(t['checkpoint_path'], model, optimizer)
-        iteration += 1                                            # the iteration after the saved one
-
-    trainset = Mel2Samp(seed=t['seed'], **data_config)
-    per_epoch = len(epoch_batches(len(trainset), t['batch_size'], t['seed'], 0, rank, num_gpus))
-    if per_epoch == 0:
-        raise ValueError("waveglow_train: %d recordings are less than one batch of %d on %d rank(s)"
-                         % (len(trainset), t['batch_size'], num_gpus))
-    if rank == 0 and not os.path.isdir(t['output_directory']):
-        os.makedirs(t['output_directory'])
-        os.chmod(t['output_directory'], 0o775)
-    logger = None
-    if t['with_tensorboard'] and rank == 0:
-        from torch.utils.tensorboard import SummaryWriter
-        logger = SummaryWriter(os.path.join(t['output_directory'], 'logs'))
-
-    model.train()
-    last = None
-    for epoch in range(iteration // per_epoch, t['epochs']):
-        print("Epoch: {}".format(epoch))
-        trainset.set_epoch(epoch)
-        batches = epoch_batches(len(trainset), t['batch_size'], t['seed'], epoch, rank, num_gpus)
-        for idx in batches[iteration % per_epoch if epoch == iteration // per_epoch else 0:]:
+    def make_step(model, optimizer, trainset, num_gpus):
+        def step(audio, mel):
             model.zero_grad()
-            audio = trainset.collate([trainset[i] for i in idx])
-            mel = trainset.batch_mels(audio)
             loss = model.training_loss(mel, audio.to(mel.device), sigma)
-            shown = reduce_tensor(loss, num_gpus) if num_gpus > 1 else loss.detach()
+            shown = vtr.shown_loss(loss, num_gpus)                # all-reduced BEFORE the backward's gradient exchange
             loss.backward()
             optimizer.step()
-            last = float(shown.item())
-            print("{}:\t{:.9f}".format(iteration, last), flush=True)
-            if logger is not None:
-                logger.add_scalar('training_loss', last, iteration)
-            if iteration % t['iters_per_checkpoint'] == 0 and rank == 0:
-                save_checkpoint(model, optimizer, learning_rate, iteration, waveglow_config,
-                                os.path.join(t['output_directory'], "waveglow_{}".format(iteration)))
-            iteration += 1
-            if t['max_iterations'] is not None and iteration > t['max_iterations']:
-                return iteration - 1, last
-    return iteration - 1, last
+            return shown
+        return step
+
+    return vtr.train(
+        WHO, num_gpus, rank, group_name, config, make_step=make_step,
+        make_model=lambda: WaveGlow(precision=precision_of(t), weight_norm=True, **waveglow_config),
+        resume=lambda model, optimizer: load_checkpoint(t['checkpoint_path'], model, optimizer)[2],
+        checkpoint=lambda *state: (_payload(*state, waveglow_config), "waveglow_{}"))
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('-c', '--config', type=str, default=None, help='JSON file with NVIDIA\'s configuration sections')
-    ap.add_argument('-r', '--rank', type=int, default=0, help='rank of this process')
-    ap.add_argument('-g', '--group_name', type=str, default='', help='name of the group of processes')
-    ap.add_argument('--n_gpus', type=int, default=None, help='number of ranks (default: WORLD_SIZE, else 1)')
-    ap.add_argument('--set', action='append', default=[], metavar='key=value', help='override a configuration key')
-    args = ap.parse_args(argv)
-    config = load_config(args.config, args.set)
-    num_gpus = args.n_gpus if args.n_gpus is not None else int(os.environ.get('WORLD_SIZE', 1))
-    return train(num_gpus, args.rank, args.group_name, config)
+    return vtr.main(WHO, __doc__, DEFAULTS, train, argv, config_help="JSON file with NVIDIA's configuration sections")
 
 
 if __name__ == '__main__':

@@ -40,6 +40,33 @@ def test_config_merging_and_set(tmp_path):
         vt.load_config(str(path))
 
 
+def test_shared_load_config_with_toy_defaults(tmp_path):
+    """``vocoder_train.load_config`` alone: the defaults and the name in the messages are the caller's."""
+    from tacotron2_amd import vocoder_train as vtr
+    toy = {'a': dict(x=1, y='s', flag=False), 'b': dict(x=2.5, z=3, deep=dict(w=0))}
+    cfg = vtr.load_config(toy, "toy_train")
+    assert cfg == toy and cfg is not toy and cfg['b']['deep'] is not toy['b']['deep']
+    cfg = vtr.load_config(toy, "toy_train", None, ["a.x=7", "b.deep.w=0.25", "y=null", "flag=true", "z=-4", "w=text"])
+    assert cfg == {'a': dict(x=7, y=None, flag=True), 'b': dict(x=2.5, z=-4, deep=dict(w='text'))}
+    assert type(cfg['a']['x']) is int and cfg['a']['flag'] is True
+    assert vtr.load_config(toy, "toy_train", None, ["b.deep.w=0.25"])['b']['deep']['w'] == 0.25
+    assert toy['a'] == dict(x=1, y='s', flag=False) and toy['b']['deep'] == dict(w=0)
+    with pytest.raises(KeyError, match=r"toy_train: configuration key x is ambiguous: \[\('a', 'x'\), \('b', 'x'\)\]"):
+        vtr.load_config(toy, "toy_train", None, ["x=1"])
+    with pytest.raises(KeyError, match="toy_train: configuration key a.z does not exist"):
+        vtr.load_config(toy, "toy_train", None, ["a.z=1"])
+    with pytest.raises(ValueError, match="toy_train: --set takes key=value, got 'z'"):
+        vtr.load_config(toy, "toy_train", None, ["z"])
+    path = tmp_path / "toy.json"
+    path.write_text(json.dumps({'b': {'z': 9, 'deep': {'w': 1}}}))
+    assert vtr.load_config(toy, "toy_train", str(path), ["z=10"])['b'] == dict(x=2.5, z=10, deep=dict(w=1))
+    path.write_text(json.dumps({'b': {'deep': {'v': 1}}}))
+    with pytest.raises(KeyError, match="toy_train: unknown configuration key b.deep.v"):
+        vtr.load_config(toy, "toy_train", str(path))
+    with pytest.raises(KeyError, match="other_train: unknown configuration key b.deep.v"):
+        vtr.load_config(toy, "other_train", str(path))
+
+
 def test_refusals():
     for bad, match in ((["precision=fp16"], "precision"), (["n_mel_channels=40"], "80 mel channels"),
                        (["segment_length=16000"], "multiple of the hop"), (["vocos_config.hop_length=128"], "not the data's"),
