@@ -938,6 +938,29 @@ int t2amd_mel_l1_fwd_f32(const float* out, const float* target, const int* lens,
 int t2amd_mel_l1_bwd_f32(const float* out, const float* target, const int* lens, const float* g, int B, int n_mel, int n,
                          int N, long long count, float* d_out, void* stream);
 
+/* Multi-resolution STFT loss (csrc/stft_loss.hip).  spec_x, spec_y: (B n, 2F) rows [re | im] of one resolution; cnt[b]: the
+ * frames of utterance b that count (device int32, clamped to [0, n]); m = sqrt(max(re^2 + im^2, eps)). */
+/* frame rows per partial slot of t2amd_stft_loss_fwd_f32 at F bins. */
+int t2amd_stft_loss_rows_per_slot(int F);
+/* slots[3 s + (0, 1, 2)] = slot s's float64 sums of (m_y - m_x)^2, m_y^2 and |ln m_x - ln m_y| over its rows' frames j < cnt[b];
+ * ceil(B n / rows_per_slot) slots, each with one writer. */
+int t2amd_stft_loss_fwd_f32(const float* spec_x, long long ldx, const float* spec_y, long long ldy, const int* cnt, int B, int n,
+                            int F, float eps, double* slots, long long slot_doubles, void* stream);
+/* One launch over R <= 8 resolutions: resolution r owns the slots [slot_off[r], slot_off[r + 1]) (host array of R + 1) and
+ * counts[r] = C_r = F_r sum_b cnt[r][b] (host array of R).  With A, Bn, Lm its three sums added in a fixed order in float64:
+ * terms[r] = (sc_r, lm_r) = (sqrt(A) / sqrt(Bn), Lm / C_r), sc_r = 0 where A == 0; coef[r] = (sc_weight / (R sqrt(A) sqrt(Bn)),
+ * 0 where A == 0; mag_weight / (R C_r)); loss[0] = sum_r (sc_weight sc_r + mag_weight lm_r) / R.  Bn == 0 gives a non-finite loss. */
+int t2amd_stft_loss_finish_f64(const double* slots, long long slot_doubles, const long long* slot_off, const double* counts,
+                               int R, float sc_weight, float mag_weight, float* loss, float* terms, float* coef, void* stream);
+/* d_spec[r] = [d_re (F) | d_im (F) | 0 (Kp - 2F)]: d_m = coef[0] (m_x - m_y) + coef[1] sign(ln m_x - ln m_y) / m_x,
+ * d_re = g[0] d_m re / m_x, d_im = g[0] d_m im / m_x where re^2 + im^2 >= eps; exactly 0 below eps and on the frames j >= cnt[b]. */
+int t2amd_stft_loss_bwd_f32(const float* spec_x, long long ldx, const float* spec_y, long long ldy, const int* cnt,
+                            const float* coef, const float* g, int B, int n, int F, int Kp, float eps, float* d_spec,
+                            long long ldd, long long d_floats, void* stream);
+/* out[i] = ((parts[i] + parts[stride + i]) + ...) + parts[(R - 1) stride + i], i < total, R <= 8. */
+int t2amd_stft_loss_sum_f32(const float* parts, long long stride, long long part_floats, int R, long long total, float* out,
+                            void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
  * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are

@@ -43,6 +43,10 @@ d_mag = d_mel . mel_basis, magnitude backward, d_frames = d_spec . forward_basis
 samples to the scalar: the term a vocoder is fine-tuned on (``tacotron2_amd.vocos_train``).  Two subgradients are definitions:
 the clamp passes the gradient where mel >= clip (torch's rule), and a bin of magnitude exactly 0 gets gradient 0 (torch's
 sqrt gives NaN there).
+
+``MultiResolutionSTFTLoss()(audio, target_audio, lengths)`` is the spectral-convergence plus log-magnitude loss over several STFT
+geometries (csrc/stft_loss.hip), again one autograd function from the samples to the scalar: fused row
+kernels straight off the two spectra, fixed-order float64 partial sums, no atomics and no host synchronisation.
 """
 import os
 
@@ -635,6 +639,162 @@ class _MelLoss(torch.autograd.Function):
         d_out = torch.empty_like(out)
         nv.mel_l1_bwd(out, tgt, lens_dev, g, ctx.count, d_out)
         d_y = stft._mel_backward(d_out, spec, mel_rows, B, T, ctx.fast)
+        return None, d_y.to(ctx.y_device), None, None, None
+
+
+class MultiResolutionSTFTLoss(torch.nn.Module):
+    """The multi-resolution STFT loss of Parallel WaveGAN between ``audio`` (carries the gradient) and ``target_audio`` (never
+    differentiated), DESIGN.md section 14.  A resolution r = (L, hop, win) is ``STFT(L, hop, win)``'s transform: reflect padding by
+    L/2, n_r = T // hop + 1 frames, F_r = L/2 + 1 bins, unnormalised basis.  With m = sqrt(max(re^2 + im^2, eps)) of either signal
+    and the sums over the whole batch, frames j < n_{r,b} = min(n_r, lengths_b // hop + 1) and all bins (C_r of them):
+
+        sc_r = sqrt(sum (m_y - m_x)^2) / sqrt(sum m_y^2)            lm_r = sum |ln m_x - ln m_y| / C_r
+        loss = (1/R) sum_r (sc_weight sc_r + mag_weight lm_r)
+
+    ``forward(audio, target_audio, lengths=None, precision='fp32')`` -> a 0-d tensor on the GPU with a ``grad_fn`` to ``audio``.
+    ``audio`` and ``target_audio`` are (B, T) or (B, 1, T) (no range check: it would cost a host synchronisation); of a longer
+    target the first T samples are used.  ``lengths`` are samples per utterance (default T); the last counted frames of a shorter
+    utterance straddle samples beyond ``lengths_b`` in both signals and still count, as in ``MelLoss``.  ``precision`` ('fp32' or
+    'bf16x3') selects the products of the backward only.  One autograd function; it keeps the two spectra of every resolution, the
+    frame counts and the coefficient buffer (``kept_state_floats``).  ``last_terms`` is the detached (R, 2) device tensor of
+    (sc_r, lm_r) of the last forward.  Three subgradients are definitions: the clamp passes the gradient where re^2 + im^2 >= eps
+    (torch's rule) and gives exactly 0 below, sign(0) = 0, and a resolution whose sum (m_y - m_x)^2 is 0 contributes gradient
+    exactly 0 through sc_r (torch gives NaN).  sum m_y^2 == 0 is not guarded (it would give a non-finite loss); with eps > 0 a silent
+    target has m_y = sqrt(eps) and cannot reach it.  There is no CPU path."""
+
+    DEFAULT_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))
+    MAX_RESOLUTIONS = 8
+
+    def __init__(self, resolutions=None, window='hann', sc_weight=1.0, mag_weight=1.0, eps=1e-7):
+        super().__init__()
+        res = self.DEFAULT_RESOLUTIONS if resolutions is None else resolutions
+        self.resolutions = self.check_resolutions(res)
+        if not float(eps) > 0.0:
+            raise ValueError("MultiResolutionSTFTLoss: eps must be positive, got %r" % (eps,))
+        self.sc_weight, self.mag_weight, self.eps = float(sc_weight), float(mag_weight), float(eps)
+        self.stfts = torch.nn.ModuleList([STFT(L, hop, win, window) for L, hop, win in self.resolutions])
+        self.last_terms = None
+        if torch.cuda.is_available():
+            self.cuda()
+
+    @classmethod
+    def check_resolutions(cls, resolutions):
+        """-> the resolutions as a tuple of (L, hop, win) int triples; ValueError with the offending values otherwise."""
+        try:
+            res = tuple(tuple(int(v) for v in r) for r in resolutions)
+        except (TypeError, ValueError):
+            raise ValueError("MultiResolutionSTFTLoss: resolutions must be (filter_length, hop_length, win_length) triples, got %r"
+                             % (resolutions,))
+        if not 1 <= len(res) <= cls.MAX_RESOLUTIONS:
+            raise ValueError("MultiResolutionSTFTLoss: 1 to %d resolutions, got %d" % (cls.MAX_RESOLUTIONS, len(res)))
+        for r in res:
+            if len(r) != 3:
+                raise ValueError("MultiResolutionSTFTLoss: a resolution is (filter_length, hop_length, win_length), got %r" % (r,))
+            L, hop, win = r
+            if L < 2 or L % 2 or hop < 1 or win < 1 or win > L or hop > L:
+                raise ValueError("MultiResolutionSTFTLoss: resolution %r needs an even filter_length >= 2, 1 <= hop_length <= "
+                                 "filter_length and 1 <= win_length <= filter_length" % (r,))
+        return res
+
+    def kept_state_floats(self, B, T):
+        """Elements kept between the forward and the backward for (B, T) samples: both spectra (B n_r, 2 F_r) of every resolution,
+        the (R, B) frame counts and the (R, 2) coefficients."""
+        R = len(self.resolutions)
+        return sum(2 * B * (T // hop + 1) * 2 * (L // 2 + 1) for L, hop, _ in self.resolutions) + R * B + 2 * R
+
+    def forward(self, audio, target_audio, lengths=None, precision='fp32'):
+        if precision not in _PRECISIONS:
+            raise ValueError("precision must be one of %s, got %r" % (sorted(_PRECISIONS), precision))
+        if audio.dim() == 3 and audio.shape[1] == 1:
+            audio = audio.reshape(audio.shape[0], audio.shape[2])
+        if target_audio.dim() == 3 and target_audio.shape[1] == 1:
+            target_audio = target_audio.reshape(target_audio.shape[0], target_audio.shape[2])
+        if audio.dim() != 2:
+            raise ValueError("MultiResolutionSTFTLoss: expected (B, T) or (B, 1, T) samples, got shape %s" % (tuple(audio.shape),))
+        B, T = audio.shape
+        if target_audio.dim() != 2 or target_audio.shape[0] != B or target_audio.shape[1] < T:
+            raise ValueError("MultiResolutionSTFTLoss: expected a (%d, >= %d) target, got shape %s" % (B, T, tuple(target_audio.shape)))
+        Lmax = max(L for L, _, _ in self.resolutions)
+        if T <= Lmax // 2:
+            raise ValueError("MultiResolutionSTFTLoss: signal of %d samples is too short to reflect-pad by %d" % (T, Lmax // 2))
+        lens = [T] * B
+        if lengths is not None:
+            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+            if len(lens) != B:
+                raise ValueError("MultiResolutionSTFTLoss: %d lengths for a batch of %d" % (len(lens), B))
+            if min(lens) < 1 or max(lens) > T:
+                raise ValueError("MultiResolutionSTFTLoss: lengths must lie in [1, %d], got %s" % (T, lens))
+        return _MultiResolutionSTFTLoss.apply(self, audio, target_audio, lens, precision)
+
+
+class _MultiResolutionSTFTLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mod, audio, target, lens, precision):
+        basis = mod.stfts[0].forward_basis
+        x = _device_signal(audio, basis)
+        dev, (B, T) = x.device, x.shape
+        y = target.detach().to(device=dev, dtype=torch.float32)
+        if y.stride(1) != 1:
+            y = y.contiguous()
+        y = y[:, :T]                                                   # a view: the pad reads the first T samples of every row
+        R = len(mod.stfts)
+        cnts = [[min(T // st.hop_length + 1, n // st.hop_length + 1) for n in lens] for st in mod.stfts]
+        cnt_dev = torch.tensor(cnts, dtype=torch.int32).to(dev)
+        specs, offs, counts = [], [0], []
+        for r, st in enumerate(mod.stfts):
+            L, hop, F = st.filter_length, st.hop_length, st.cutoff
+            n = T // hop + 1
+            ldo = (T + L + 3) // 4 * 4
+            padded = torch.empty(2 * B, ldo, dtype=torch.float32, device=dev)
+            nv.reflect_pad(x, padded[:B], L // 2)
+            nv.reflect_pad(y, padded[B:], L // 2)
+            spec = torch.empty(2 * B * n, 2 * F, dtype=torch.float32, device=dev)       # rows of x, then rows of y
+            frames0 = padded.as_strided((n, L), (hop, 1))
+            nv.gemm(spec[:n], frames0, st.forward_basis.view(2 * F, L), batch=2 * B, strides=(ldo, 0, n * 2 * F))
+            specs.append(spec)
+            offs.append(offs[-1] + nv.stft_loss_slots(B * n, F))
+            counts.append(F * sum(cnts[r]))
+        slots = torch.empty(3 * offs[-1], dtype=torch.float64, device=dev)
+        for r, st in enumerate(mod.stfts):
+            rows = specs[r].shape[0] // 2
+            nv.stft_loss_fwd(specs[r][:rows], specs[r][rows:], cnt_dev[r], rows // B, st.cutoff, mod.eps,
+                             slots[3 * offs[r]:3 * offs[r + 1]])
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        terms = torch.empty(R, 2, dtype=torch.float32, device=dev)
+        coef = torch.empty(R, 2, dtype=torch.float32, device=dev)
+        nv.stft_loss_finish(slots, offs, counts, mod.sc_weight, mod.mag_weight, loss, terms, coef)
+        mod.last_terms = terms
+        ctx.mod, ctx.kept, ctx.fast = mod, (specs, cnt_dev, coef), _PRECISIONS[precision]
+        ctx.y_shape, ctx.y_device = (B, T), audio.device
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.kept is None:
+            raise RuntimeError("MultiResolutionSTFTLoss: backward was already run; the kept state is freed by the first one")
+        specs, cnt_dev, coef = ctx.kept
+        ctx.kept = None
+        mod, (B, T) = ctx.mod, ctx.y_shape
+        dev = coef.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        g = g.to(device=dev, dtype=torch.float32).reshape(1).contiguous()
+        R = len(mod.stfts)
+        parts = torch.empty(R, B, T, **f32)
+        for r, st in enumerate(mod.stfts):
+            L, hop, F = st.filter_length, st.hop_length, st.cutoff
+            tab = st.bwd_tables(dev)
+            rows = specs[r].shape[0] // 2
+            d_spec = torch.empty(rows, tab["Kp"], **f32)
+            nv.stft_loss_bwd(specs[r][:rows], specs[r][rows:], cnt_dev[r], coef[r], g, rows // B, F, mod.eps, d_spec)
+            specs[r] = None
+            d_frames = torch.empty(rows, L, **f32)
+            nv.gemm(d_frames, d_spec, tab["fbt"], fast=ctx.fast)
+            nv.stft_frames_fold(d_frames, parts[r], hop, L // 2)
+        if R == 1:
+            d_y = parts[0]
+        else:
+            d_y = torch.empty(B, T, **f32)
+            nv.stft_loss_sum(parts, d_y)                               # r = 0 .. R - 1 in order, one writer per sample
         return None, d_y.to(ctx.y_device), None, None, None
 
 

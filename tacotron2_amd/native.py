@@ -287,6 +287,8 @@ SYMBOLS = [
     "t2amd_reflect_pad_f32", "t2amd_reflect_index", "t2amd_stft_magnitude_f32", "t2amd_mel_log_compress_f32",
     "t2amd_mel_log_bwd_f32", "t2amd_stft_magnitude_bwd_f32", "t2amd_stft_frames_fold_f32", "t2amd_mel_l1_rows_per_slot",
     "t2amd_mel_l1_fwd_f32", "t2amd_mel_l1_bwd_f32",
+    "t2amd_stft_loss_rows_per_slot", "t2amd_stft_loss_fwd_f32", "t2amd_stft_loss_finish_f64", "t2amd_stft_loss_bwd_f32",
+    "t2amd_stft_loss_sum_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
@@ -397,6 +399,11 @@ def _argtypes():
         "t2amd_mel_l1_rows_per_slot": [_I],
         "t2amd_mel_l1_fwd_f32": [_P, _P, _P, _I, _I, _I, _I, _L, _P, _L, _P],
         "t2amd_mel_l1_bwd_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _L, _P, _P],
+        "t2amd_stft_loss_rows_per_slot": [_I],
+        "t2amd_stft_loss_fwd_f32": [_P, _L, _P, _L, _P, _I, _I, _I, _F, _P, _L, _P],
+        "t2amd_stft_loss_finish_f64": [_P, _L, _P, _P, _I, _F, _F, _P, _P, _P, _P],
+        "t2amd_stft_loss_bwd_f32": [_P, _L, _P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _P, _L, _L, _P],
+        "t2amd_stft_loss_sum_f32": [_P, _L, _L, _I, _L, _P, _P],
         "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
         "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
@@ -1714,6 +1721,69 @@ def mel_l1_bwd(out, target, lens, g, count, d_out):
     _check(load().t2amd_mel_l1_bwd_f32(ptr(_fullc(out)), ptr(_fullc(target)), None if lens is None else ptr(lens, torch.int32),
                                        ptr(_fullc(g)), B, n_mel, n, N, _i64(int(count)), ptr(_fullc(d_out)), _stream()),
            "t2amd_mel_l1_bwd_f32")
+
+
+# ---- multi-resolution STFT loss (csrc/stft_loss.hip) -----------------------------------------------------------------------
+def stft_loss_slots(rows, F):
+    """Partial slots (three float64 sums each) of ``stft_loss_fwd`` for `rows` frame rows of F bins."""
+    return -(-int(rows) // int(load().t2amd_stft_loss_rows_per_slot(int(F))))
+
+
+def _stft_loss_args(who, spec_x, spec_y, cnt, n, F):
+    px, ldx, R, Cx = _mat(spec_x)
+    py, ldy, Ry, Cy = _mat(spec_y)
+    n, F = int(n), int(F)
+    if Ry != R or Cx < 2 * F or Cy < 2 * F or n < 1 or R % n:
+        raise NativeError("%s: shape mismatch spec_x=%s spec_y=%s n=%d F=%d" % (who, tuple(spec_x.shape), tuple(spec_y.shape), n, F))
+    B = R // n
+    if cnt is None or cnt.dtype != torch.int32 or cnt.dim() != 1 or cnt.numel() != B or not cnt.is_contiguous():
+        raise NativeError("%s: cnt must be a contiguous int32 vector of %d frame counts" % (who, B))
+    return px, ldx, py, ldy, B
+
+
+def stft_loss_fwd(spec_x, spec_y, cnt, n, F, eps, slots):
+    """slots (float64, 3 per slot) = the partial sums of (m_y - m_x)^2, m_y^2 and |ln m_x - ln m_y| over the frames j < cnt[b];
+    spec_x, spec_y (B n, 2F) rows [re | im].  ``stft_loss_finish`` combines them."""
+    px, ldx, py, ldy, B = _stft_loss_args("stft_loss_fwd", spec_x, spec_y, cnt, n, F)
+    _check(load().t2amd_stft_loss_fwd_f32(px, _i64(ldx), py, _i64(ldy), ptr(cnt, torch.int32), B, int(n), int(F), C.c_float(eps),
+                                          ptr(_fullc(slots), torch.float64), _i64(slots.numel()), _stream()),
+           "t2amd_stft_loss_fwd_f32")
+
+
+def stft_loss_finish(slots, offsets, counts, sc_weight, mag_weight, loss, terms, coef):
+    """loss (1,), terms (R, 2) = (sc_r, lm_r) and coef (R, 2) from every resolution's slots; ``offsets`` (R + 1 slot indices)
+    and ``counts`` (R values C_r) are host lists."""
+    R = len(counts)
+    if len(offsets) != R + 1 or loss.numel() != 1 or terms.numel() != 2 * R or coef.numel() != 2 * R:
+        raise NativeError("stft_loss_finish: %d offsets, %d counts, loss of %d, terms of %d, coef of %d elements"
+                          % (len(offsets), R, loss.numel(), terms.numel(), coef.numel()))
+    off = (C.c_longlong * (R + 1))(*[int(v) for v in offsets])
+    cnt = (C.c_double * max(R, 1))(*[float(v) for v in counts])
+    _check(load().t2amd_stft_loss_finish_f64(ptr(_fullc(slots), torch.float64), _i64(slots.numel()), off, cnt, R,
+                                             C.c_float(sc_weight), C.c_float(mag_weight), ptr(_fullc(loss)), ptr(_fullc(terms)),
+                                             ptr(_fullc(coef)), _stream()), "t2amd_stft_loss_finish_f64")
+
+
+def stft_loss_bwd(spec_x, spec_y, cnt, coef, g, n, F, eps, d_spec):
+    """d_spec (B n, Kp) = [d_re | d_im | 0] of one resolution from its spectra, its two coefficients ``coef`` (2,) and the upstream
+    scalar ``g`` (one-element device tensor); 0 below eps and outside the mask."""
+    px, ldx, py, ldy, B = _stft_loss_args("stft_loss_bwd", spec_x, spec_y, cnt, n, F)
+    pd, ldd, Rd, Kp = _mat(d_spec)
+    if Rd != B * int(n) or Kp < 2 * int(F) or coef.numel() != 2 or g.numel() != 1:
+        raise NativeError("stft_loss_bwd: shape mismatch d_spec=%s for %d rows of F=%d, coef of %d, g of %d elements"
+                          % (tuple(d_spec.shape), B * int(n), F, coef.numel(), g.numel()))
+    _check(load().t2amd_stft_loss_bwd_f32(px, _i64(ldx), py, _i64(ldy), ptr(cnt, torch.int32), ptr(_fullc(coef)), ptr(_fullc(g)), B,
+                                          int(n), int(F), int(Kp), C.c_float(eps), pd, _i64(ldd), _i64(_floats(d_spec)), _stream()),
+           "t2amd_stft_loss_bwd_f32")
+
+
+def stft_loss_sum(parts, out):
+    """out = ((parts[0] + parts[1]) + ...) + parts[R - 1]; parts (R, ...) contiguous, out of one part's shape."""
+    R = parts.shape[0]
+    if parts.dim() < 2 or tuple(parts.shape[1:]) != tuple(out.shape):
+        raise NativeError("stft_loss_sum: parts %s beside out %s" % (tuple(parts.shape), tuple(out.shape)))
+    _check(load().t2amd_stft_loss_sum_f32(ptr(_fullc(parts)), _i64(out.numel()), _i64(parts.numel()), int(R), _i64(out.numel()),
+                                          ptr(_fullc(out)), _stream()), "t2amd_stft_loss_sum_f32")
 
 
 # ----------------------------------------------------------------------------
