@@ -36,6 +36,9 @@ Ragged batches run in one packed frame space (utterance b owns n_b + ceil(L/hop)
 cover sum(n_b + 3) rows at L = 1024, hop = 256, not B * n_max.  The mel inversion is the clamped pseudo-inverse
 max(pinv(mel_basis) . exp(mel), 0) (the reference gives no recipe).
 
+Steps 1 and 2 are ``STFT.frame_spectra`` for every transform of this file (the mel path, ``STFT.transform``, the STFT loss), and
+``STFT.spectrum_backward`` (d_frames = d_spec . forward_basis, overlap-add with the reflect fold) is the tail of every backward.
+
 The way back (csrc/audio_bwd.hip): ``mel_spectrogram`` of a signal that requires grad returns the same
 bits with a ``grad_fn``; it keeps the spectrum and the mel rows and its backward is five launches (log-compress backward,
 d_mag = d_mel . mel_basis, magnitude backward, d_frames = d_spec . forward_basis, overlap-add with the reflect fold).
@@ -54,6 +57,7 @@ import numpy as np
 import torch
 
 from . import native as nv
+from .vocoder import host_lengths
 
 _F_SP = 200.0 / 3.0                  # Slaney: linear below 1 kHz, 200/3 Hz per mel
 _MIN_LOG_HZ = 1000.0
@@ -180,6 +184,59 @@ def packed_rows(lengths, filter_length=1024, hop_length=256):
 _PRECISIONS = {'fp32': 0, 'bf16x3': 1}
 
 
+def _precision(precision):
+    if precision not in _PRECISIONS:
+        raise ValueError("precision must be one of %s, got %r" % (sorted(_PRECISIONS), precision))
+    return _PRECISIONS[precision]
+
+
+def _require_device(t, dry_run=True):
+    """The modules of this file have no CPU path; validate-only mode passes when ``dry_run``."""
+    if not t.is_cuda and not (dry_run and nv.validate_only()):
+        raise nv.NativeError("tacotron2_amd.audio: move the module to the MI355X first (.cuda()); there is no CPU path")
+
+
+def _device_signal(y, like):
+    if y.dim() != 2:
+        raise ValueError("expected (B, T) samples, got shape %s" % (tuple(y.shape),))
+    _require_device(like)
+    return y.detach().to(device=like.device, dtype=torch.float32).contiguous()
+
+
+def _squeeze_channel(x):
+    """(B, 1, T) -> (B, T); anything else as it is."""
+    return x.reshape(x.shape[0], x.shape[2]) if x.dim() == 3 and x.shape[1] == 1 else x
+
+
+def _lengths(lengths, B, hi, who="", full=None):
+    """``vocoder.host_lengths`` with the count checked and, where ``hi`` is given, the range [1, hi]; None stays None unless
+    ``full`` is given.  ``who`` prefixes the error text."""
+    if lengths is None and full is None:
+        return None
+    lens = host_lengths(lengths, B, full)
+    if len(lens) != B:
+        raise ValueError("%s%d lengths for a batch of %d" % (who, len(lens), B))
+    if hi is not None and (min(lens) < 1 or max(lens) > hi):
+        raise ValueError("%slengths must lie in [1, %d], got %s" % (who, hi, lens))
+    return lens
+
+
+def _per_device(cache, name, device, build):
+    """``build(device)`` once per (name, device): the tables that are plain attributes, not buffers, built on first use."""
+    key = (name, torch.device(device))
+    if key not in cache:
+        cache[key] = build(key[1])
+    return cache[key]
+
+
+def _take_kept(ctx, who):
+    """The state an autograd function kept for its backward, taken and freed."""
+    kept, ctx.kept = ctx.kept, None
+    if kept is None:
+        raise RuntimeError("%s: backward was already run; the kept state is freed by the first one" % who)
+    return kept
+
+
 class STFT(torch.nn.Module):
     """reference stft.py:42-141 on the GPU: forward transform (magnitude, phase), inverse, reconstruction."""
 
@@ -189,44 +246,67 @@ class STFT(torch.nn.Module):
         self.cutoff = filter_length // 2 + 1
         basis = torch.from_numpy(fourier_basis(filter_length, win_length, window))
         self.register_buffer('forward_basis', basis[:, None, :].contiguous())      # (2F, 1, L) like the reference
-        self._gl_tables = {}            # per device: interleaved bases, squared window (plain attributes, not buffers)
-        self._bwd_tables = {}           # per device: the transposed basis of the backward pass
+        self.Fpad = (self.cutoff + 15) // 16 * 16       # bins rounded up to the 16-wide column tiles of the row kernels
+        self._lazy = {}                 # per device: the tables below (plain attributes, not buffers)
 
     def gl_tables(self, device):
         """Device tables of the inverse / Griffin-Lim path, built on first use: ``fbi`` (2F, L) forward basis with re/im
-        rows interleaved, ``ibt`` (L, 2Fp) inverse basis transposed with interleaved columns (zero beyond 2F), ``wsq``
+        rows interleaved, ``ibt`` (L, 2 Fpad) inverse basis transposed with interleaved columns (zero beyond 2F), ``wsq``
         (L,) float64 squared window."""
-        device = torch.device(device)
-        t = self._gl_tables.get(device)
-        if t is None:
+        def build(device):
             L, F = self.filter_length, self.cutoff
-            Fp = (F + 15) // 16 * 16
             fb = self.forward_basis.view(2 * F, L).to(device)
             perm = torch.stack([torch.arange(F), torch.arange(F) + F], 1).reshape(-1).to(device)
             ib = inverse_basis(L, self.hop_length, self.win_length, self.window)
-            ibt = np.zeros((L, 2 * Fp), dtype=np.float32)
+            ibt = np.zeros((L, 2 * self.Fpad), dtype=np.float32)
             ibt[:, 0:2 * F:2] = ib[:F].T
             ibt[:, 1:2 * F:2] = ib[F:].T
             wsq = _squared_window(self.window, self.win_length, L) if self.window is not None else np.ones(L)
-            t = {"fbi": fb.index_select(0, perm).contiguous(), "ibt": torch.from_numpy(ibt).to(device),
-                 "wsq": torch.from_numpy(np.ascontiguousarray(wsq, dtype=np.float64)).to(device), "Fp": Fp}
-            self._gl_tables[device] = t
-        return t
+            return {"fbi": fb.index_select(0, perm).contiguous(), "ibt": torch.from_numpy(ibt).to(device),
+                    "wsq": torch.from_numpy(np.ascontiguousarray(wsq, dtype=np.float64)).to(device)}
+        return _per_device(self._lazy, 'gl', device, build)
 
     def bwd_tables(self, device):
-        """Device table of the backward of the forward transform, built on first use (a plain attribute like ``gl_tables``):
-        ``fbt`` (L, Kp) = forward_basis transposed, Kp = 2F rounded up to the 32-deep k-steps of the split-bf16 GEMM, zero
-        columns beyond 2F (the B operand of d_frames = d_spec . forward_basis)."""
-        device = torch.device(device)
-        t = self._bwd_tables.get(device)
-        if t is None:
+        """Device table of the backward of the forward transform, built on first use: ``fbt`` (L, Kp) = forward_basis
+        transposed, Kp = 2F rounded up to the 32-deep k-steps of the split-bf16 GEMM, zero columns beyond 2F (the B operand of
+        d_frames = d_spec . forward_basis)."""
+        def build(device):
             L, F = self.filter_length, self.cutoff
             Kp = (2 * F + 31) // 32 * 32
             fbt = torch.zeros(L, Kp, dtype=torch.float32, device=device)
             fbt[:, :2 * F] = self.forward_basis.view(2 * F, L).to(device).t()
-            t = {"fbt": fbt, "Kp": Kp}
-            self._bwd_tables[device] = t
-        return t
+            return {"fbt": fbt, "Kp": Kp}
+        return _per_device(self._lazy, 'bwd', device, build)
+
+    def frame_spectra(self, signals, basis, width):
+        """The front end of every transform here: ``signals``, a list of (B, T) device float32 signals of equal T, each
+        reflect-padded by L/2 into one buffer of rows of (T + L + 3) // 4 * 4 floats, then ONE GEMM over all of them,
+        spec = frames . basis^T with batch = len(signals) B.  The frame matrix is never built: the A operand is the padded
+        signal at row stride ``hop`` (rows overlap).  ``basis`` (2F, L) is ``forward_basis`` (rows [re | im]) or the
+        interleaved ``fbi``; ``width`` >= 2F is the row width of the result.  -> (spec (len(signals) B n, width), n)."""
+        B, T = signals[0].shape
+        L, hop, F, dev = self.filter_length, self.hop_length, self.cutoff, signals[0].device
+        if T <= L // 2:
+            raise ValueError("signal of %d samples is too short to reflect-pad by %d" % (T, L // 2))
+        n, batch = T // hop + 1, len(signals) * B
+        ldo = (T + L + 3) // 4 * 4
+        padded = torch.empty(batch, ldo, dtype=torch.float32, device=dev)
+        for i, sig in enumerate(signals):
+            nv.reflect_pad(sig, padded[i * B:(i + 1) * B], L // 2)
+        spec = torch.empty(batch * n, width, dtype=torch.float32, device=dev)
+        frames0 = padded.as_strided((n, L), (hop, 1))                              # utterance 0; rows overlap
+        nv.gemm(spec[:n, :2 * F], frames0, basis, batch=batch, strides=(ldo, 0, n * width))
+        return spec, n
+
+    def spectrum_backward(self, d_spec, B, T, fast, out=None):
+        """The tail of every backward here: d_y (B, T) from d_spec (B n, Kp) rows [d_re | d_im | 0], d_frames = d_spec .
+        forward_basis on the GEMM, then the overlap-add with the fold of the reflect padding, into ``out`` when given."""
+        L = self.filter_length
+        d_frames = torch.empty(d_spec.shape[0], L, dtype=torch.float32, device=d_spec.device)
+        nv.gemm(d_frames, d_spec, self.bwd_tables(d_spec.device)["fbt"], fast=fast)
+        d_y = torch.empty(B, T, dtype=torch.float32, device=d_spec.device) if out is None else out
+        nv.stft_frames_fold(d_frames, d_y, self.hop_length, L // 2)
+        return d_y
 
     def magnitude_rows(self, y):
         """y (B, T) device f32 -> (mag (B*n, Fpad) with zero columns beyond F, n)."""
@@ -235,19 +315,9 @@ class STFT(torch.nn.Module):
 
     def _magnitude_spec_rows(self, y):
         """``magnitude_rows`` with the spectrum it came from: (mag, spec (B*n, 2F) rows [re | im], n)."""
-        B, T = y.shape
-        L, hop, F = self.filter_length, self.hop_length, self.cutoff
-        if T <= L // 2:
-            raise ValueError("signal of %d samples is too short to reflect-pad by %d" % (T, L // 2))
-        n = T // hop + 1
-        ldo = (T + L + 3) // 4 * 4
-        padded = torch.empty(B, ldo, dtype=torch.float32, device=y.device)
-        nv.reflect_pad(y, padded, L // 2)
-        spec = torch.empty(B * n, 2 * F, dtype=torch.float32, device=y.device)
-        frames0 = padded.as_strided((n, L), (hop, 1))                              # utterance 0; rows overlap
-        nv.gemm(spec[:n], frames0, self.forward_basis.view(2 * F, L), batch=B, strides=(ldo, 0, n * 2 * F))
-        Fpad = (F + 15) // 16 * 16
-        mag = torch.empty(B * n, Fpad, dtype=torch.float32, device=y.device)
+        F = self.cutoff
+        spec, n = self.frame_spectra([y], self.forward_basis.view(2 * F, self.filter_length), 2 * F)
+        mag = torch.empty(spec.shape[0], self.Fpad, dtype=torch.float32, device=y.device)
         nv.stft_magnitude(spec, mag, F)
         return mag, spec, n
 
@@ -261,27 +331,10 @@ class STFT(torch.nn.Module):
         return out
 
 
-    def _spec_rows(self, y):
-        """y (B, T) device f32 -> (spec (B*n, 2Fp) interleaved re/im rows, n)."""
-        B, T = y.shape
-        L, hop, F = self.filter_length, self.hop_length, self.cutoff
-        if T <= L // 2:
-            raise ValueError("signal of %d samples is too short to reflect-pad by %d" % (T, L // 2))
-        tab = self.gl_tables(y.device)
-        Fp = tab["Fp"]
-        n = T // hop + 1
-        ldo = (T + L + 3) // 4 * 4
-        padded = torch.empty(B, ldo, dtype=torch.float32, device=y.device)
-        nv.reflect_pad(y, padded, L // 2)
-        spec = torch.empty(B * n, 2 * Fp, dtype=torch.float32, device=y.device)
-        frames0 = padded.as_strided((n, L), (hop, 1))
-        nv.gemm(spec[:n, :2 * F], frames0, tab["fbi"], batch=B, strides=(ldo, 0, n * 2 * Fp))
-        return spec, n
-
     def transform(self, input_data):
         """(magnitude, phase), each (B, F, n): reference stft.py:77-105 (phase = atan2(im, re))."""
         y = _device_signal(input_data, self.forward_basis)
-        spec, n = self._spec_rows(y)
+        spec, n = self.frame_spectra([y], self.gl_tables(y.device)["fbi"], 2 * self.Fpad)
         B, F = y.shape[0], self.cutoff
         mag = torch.empty(B, F, n, dtype=torch.float32, device=y.device)
         phase = torch.empty(B, F, n, dtype=torch.float32, device=y.device)
@@ -304,33 +357,21 @@ class _GriffinLim:
     iteration loop (run) issues four launches per iteration and no allocation, copy or synchronisation."""
 
     def __init__(self, stft, magnitudes, angles, lengths, precision):
-        if precision not in _PRECISIONS:
-            raise ValueError("precision must be one of %s, got %r" % (sorted(_PRECISIONS), precision))
-        self.fast = _PRECISIONS[precision]
-        basis = stft.forward_basis
-        if not basis.is_cuda and not nv.validate_only():
-            raise nv.NativeError("tacotron2_amd.audio: move the module to the MI355X first (.cuda()); there is no CPU path")
-        dev = basis.device
+        self.fast = _precision(precision)
+        _require_device(stft.forward_basis)
+        dev = stft.forward_basis.device
         L, hop, F = stft.filter_length, stft.hop_length, stft.cutoff
         mag = magnitudes.detach().to(device=dev, dtype=torch.float32).contiguous()
         if mag.dim() != 3 or mag.shape[1] != F:
             raise ValueError("expected (B, %d, n) magnitudes, got shape %s" % (F, tuple(mag.shape)))
         B, _, n = mag.shape
-        if lengths is None:
-            lens = [n] * B
-        else:
-            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-            if len(lens) != B:
-                raise ValueError("%d lengths for a batch of %d" % (len(lens), B))
-            if min(lens) < 1 or max(lens) > n:
-                raise ValueError("lengths must lie in [1, %d], got %s" % (n, lens))
+        lens = _lengths(lengths, B, n, full=n)
         ph = None
         if angles is not None:
             ph = torch.as_tensor(angles).detach().to(device=dev, dtype=torch.float32).contiguous()
             if tuple(ph.shape) != tuple(mag.shape):
                 raise ValueError("angles %s do not match the magnitudes %s" % (tuple(ph.shape), tuple(mag.shape)))
-        tab = stft.gl_tables(dev)
-        Fp = tab["Fp"]
+        tab, Fp = stft.gl_tables(dev), stft.Fpad
         c = -(-L // hop)
         rows = np.asarray(lens, dtype=np.int64) + c - 1
         row0 = np.concatenate([[0], np.cumsum(rows)])
@@ -391,14 +432,6 @@ def griffin_lim(magnitudes, stft_fn, n_iters=30, angles=None, lengths=None, prec
     return _GriffinLim(stft_fn, magnitudes, angles, lengths, precision).run(int(n_iters))
 
 
-def _device_signal(y, like):
-    if y.dim() != 2:
-        raise ValueError("expected (B, T) samples, got shape %s" % (tuple(y.shape),))
-    if not like.is_cuda and not nv.validate_only():
-        raise nv.NativeError("tacotron2_amd.audio: move the module to the MI355X first (.cuda()); there is no CPU path")
-    return y.detach().to(device=like.device, dtype=torch.float32).contiguous()
-
-
 class TacotronSTFT(torch.nn.Module):
     def __init__(self, filter_length=1024, hop_length=256, win_length=1024, n_mel_channels=80,
                  sampling_rate=22050, mel_fmin=0.0, mel_fmax=8000.0):
@@ -408,13 +441,10 @@ class TacotronSTFT(torch.nn.Module):
         self.stft_fn = STFT(filter_length, hop_length, win_length)
         fb = mel_filterbank(sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax)
         self.register_buffer('mel_basis', torch.from_numpy(fb).float())
-        F = self.stft_fn.cutoff
-        Fpad = (F + 15) // 16 * 16
-        padded = torch.zeros(n_mel_channels, Fpad, dtype=torch.float32)
-        padded[:, :F] = self.mel_basis
+        padded = torch.zeros(n_mel_channels, self.stft_fn.Fpad, dtype=torch.float32)
+        padded[:, :self.stft_fn.cutoff] = self.mel_basis
         self.register_buffer('_mel_basis_padded', padded, persistent=False)
-        self._mel_pinv = {}             # per device, built on first use by mel_to_magnitude (not a buffer)
-        self._mel_basis_t = {}          # per device, built on first use by the backward pass (not a buffer)
+        self._lazy = {}                 # per device: mel_pinv and mel_basis_t, built on first use (not buffers)
         self.clip_val = 1e-5
         if torch.cuda.is_available():
             self.cuda()
@@ -430,12 +460,8 @@ class TacotronSTFT(torch.nn.Module):
     def mel_pinv(self, device):
         """(F, n_mel) float32 pseudo-inverse of the mel filterbank (float64 pinv of the float32 ``mel_basis``), built on
         first use (not a buffer)."""
-        device = torch.device(device)
-        p = self._mel_pinv.get(device)
-        if p is None:
-            p = torch.from_numpy(np.linalg.pinv(self.mel_basis.cpu().double().numpy()).astype(np.float32)).to(device)
-            self._mel_pinv[device] = p
-        return p
+        return _per_device(self._lazy, 'pinv', device, lambda d: torch.from_numpy(
+            np.linalg.pinv(self.mel_basis.cpu().double().numpy()).astype(np.float32)).to(d))
 
     def mel_to_magnitude(self, mel, lengths=None):
         """Log-mel (B, n_mel, n) -> linear magnitudes (B, F, n) = max(pinv(mel_basis) . exp(mel), 0), zero beyond
@@ -443,19 +469,13 @@ class TacotronSTFT(torch.nn.Module):
         inverse of the filterbank.  fp16 / bf16 mels are cast to float32."""
         if mel.dim() != 3 or mel.shape[1] != self.n_mel_channels:
             raise ValueError("expected (B, %d, n) log-mels, got shape %s" % (self.n_mel_channels, tuple(mel.shape)))
-        if not self.mel_basis.is_cuda:
-            raise nv.NativeError("tacotron2_amd.audio: move the module to the MI355X first (.cuda()); there is no CPU path")
+        _require_device(self.mel_basis, dry_run=False)
         dev = self.mel_basis.device
         mel = mel.detach().to(device=dev, dtype=torch.float32).contiguous()
         B, n_mel, n = mel.shape
-        F = self.stft_fn.cutoff
-        Fp = (F + 15) // 16 * 16
-        lens_dev = lens = None
-        if lengths is not None:
-            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-            if len(lens) != B:
-                raise ValueError("%d lengths for a batch of %d" % (len(lens), B))
-            lens_dev = torch.tensor(lens, dtype=torch.int32).to(dev)
+        F, Fp = self.stft_fn.cutoff, self.stft_fn.Fpad
+        lens = _lengths(lengths, B, None)
+        lens_dev = None if lens is None else torch.tensor(lens, dtype=torch.int32).to(dev)
         ldk = (n_mel + 3) // 4 * 4
         rows = torch.empty(B * n, ldk, dtype=torch.float32, device=dev)
         nv.mel_decompress(mel, rows, lens, lens_dev)
@@ -474,12 +494,7 @@ class TacotronSTFT(torch.nn.Module):
     def mel_basis_t(self, device):
         """(Fpad, n_mel) float32: the zero-padded filterbank transposed, the B operand of d_mag = d_mel . mel_basis; built on
         first use (not a buffer)."""
-        device = torch.device(device)
-        t = self._mel_basis_t.get(device)
-        if t is None:
-            t = self._mel_basis_padded.to(device).t().contiguous()
-            self._mel_basis_t[device] = t
-        return t
+        return _per_device(self._lazy, 'basis_t', device, lambda d: self._mel_basis_padded.to(d).t().contiguous())
 
     def _check_range(self, y):
         lo, hi = (float(v) for v in torch.stack(torch.aminmax(y)).tolist())
@@ -505,21 +520,15 @@ class TacotronSTFT(torch.nn.Module):
     def _mel_backward(self, d_out, spec, mel_rows, B, T, fast):
         """d_y (B, T) float32 from d_out (B, n_mel, n) and the kept spectrum and mel rows: five launches."""
         st = self.stft_fn
-        L, hop, F = st.filter_length, st.hop_length, st.cutoff
         dev, R = spec.device, spec.shape[0]
         f32 = dict(dtype=torch.float32, device=dev)
-        tab = st.bwd_tables(dev)
         d_mel = torch.empty(R, self.n_mel_channels, **f32)
         nv.mel_log_bwd(d_out, mel_rows, d_mel, self.clip_val)
-        d_mag = torch.empty(R, (F + 15) // 16 * 16, **f32)
+        d_mag = torch.empty(R, st.Fpad, **f32)
         nv.gemm(d_mag, d_mel, self.mel_basis_t(dev), fast=fast)
-        d_spec = torch.empty(R, tab["Kp"], **f32)
-        nv.stft_magnitude_bwd(d_mag, spec, d_spec, F)
-        d_frames = torch.empty(R, L, **f32)
-        nv.gemm(d_frames, d_spec, tab["fbt"], fast=fast)
-        d_y = torch.empty(B, T, **f32)
-        nv.stft_frames_fold(d_frames, d_y, hop, L // 2)
-        return d_y
+        d_spec = torch.empty(R, st.bwd_tables(dev)["Kp"], **f32)
+        nv.stft_magnitude_bwd(d_mag, spec, d_spec, st.cutoff)
+        return st.spectrum_backward(d_spec, B, T, fast)
 
     def mel_spectrogram(self, y, check_range=True, precision='fp32'):
         """y (B, T) float in [-1, 1] -> (B, n_mel_channels, T // hop + 1) on the GPU.
@@ -530,8 +539,7 @@ class TacotronSTFT(torch.nn.Module):
         subgradients are definitions: the gradient passes where mel >= clip_val (torch's clamp rule), and a bin whose
         magnitude is exactly 0 gets gradient 0, where torch's sqrt gives NaN.  The range check costs a host
         synchronisation: training callers pass ``check_range=False``."""
-        if precision not in _PRECISIONS:
-            raise ValueError("precision must be one of %s, got %r" % (sorted(_PRECISIONS), precision))
+        _precision(precision)
         if torch.is_grad_enabled() and torch.is_tensor(y) and y.requires_grad:
             return _MelSpectrogram.apply(self, y, check_range, precision)
         y = _device_signal(y, self.mel_basis)
@@ -553,10 +561,7 @@ class _MelSpectrogram(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_out):
-        if ctx.kept is None:
-            raise RuntimeError("mel_spectrogram: backward was already run; the kept state is freed by the first one")
-        spec, mel_rows = ctx.kept
-        ctx.kept = None
+        spec, mel_rows = _take_kept(ctx, "mel_spectrogram")
         d_out = d_out.to(device=spec.device, dtype=torch.float32).contiguous()
         d_y = ctx.stft._mel_backward(d_out, spec, mel_rows, ctx.y_shape[0], ctx.y_shape[1], ctx.fast)
         return None, d_y.to(ctx.y_device), None, None
@@ -580,10 +585,8 @@ class MelLoss(torch.nn.Module):
 
     def forward(self, audio, target_mel, lengths=None, precision='fp32'):
         st = self.stft
-        if precision not in _PRECISIONS:
-            raise ValueError("precision must be one of %s, got %r" % (sorted(_PRECISIONS), precision))
-        if audio.dim() == 3 and audio.shape[1] == 1:
-            audio = audio.reshape(audio.shape[0], audio.shape[2])
+        _precision(precision)
+        audio = _squeeze_channel(audio)
         if audio.dim() != 2:
             raise ValueError("MelLoss: expected (B, T) or (B, 1, T) samples, got shape %s" % (tuple(audio.shape),))
         B, T = audio.shape
@@ -593,15 +596,8 @@ class MelLoss(torch.nn.Module):
         n, N = T // st.stft_fn.hop_length + 1, target_mel.shape[2]
         if N < 1 or N > n:
             raise ValueError("MelLoss: the target has %d frames, %d samples give %d" % (N, T, n))
-        lens = None
-        if lengths is not None:
-            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-            if len(lens) != B:
-                raise ValueError("MelLoss: %d lengths for a batch of %d" % (len(lens), B))
-            if min(lens) < 1 or max(lens) > N:
-                raise ValueError("MelLoss: lengths must lie in [1, %d], got %s" % (N, lens))
-        if not st.mel_basis.is_cuda and not nv.validate_only():
-            raise nv.NativeError("tacotron2_amd.audio: move the module to the MI355X first (.cuda()); there is no CPU path")
+        lens = _lengths(lengths, B, N, "MelLoss: ")
+        _require_device(st.mel_basis)
         return _MelLoss.apply(st, audio, target_mel, lens, precision)
 
 
@@ -626,10 +622,7 @@ class _MelLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.kept is None:
-            raise RuntimeError("MelLoss: backward was already run; the kept state is freed by the first one")
-        spec, mel_rows, tgt, lens_dev = ctx.kept
-        ctx.kept = None
+        spec, mel_rows, tgt, lens_dev = _take_kept(ctx, "MelLoss")
         stft, (B, T) = ctx.stft, ctx.y_shape
         dev = spec.device
         n = spec.shape[0] // B
@@ -703,12 +696,8 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
         return sum(2 * B * (T // hop + 1) * 2 * (L // 2 + 1) for L, hop, _ in self.resolutions) + R * B + 2 * R
 
     def forward(self, audio, target_audio, lengths=None, precision='fp32'):
-        if precision not in _PRECISIONS:
-            raise ValueError("precision must be one of %s, got %r" % (sorted(_PRECISIONS), precision))
-        if audio.dim() == 3 and audio.shape[1] == 1:
-            audio = audio.reshape(audio.shape[0], audio.shape[2])
-        if target_audio.dim() == 3 and target_audio.shape[1] == 1:
-            target_audio = target_audio.reshape(target_audio.shape[0], target_audio.shape[2])
+        _precision(precision)
+        audio, target_audio = _squeeze_channel(audio), _squeeze_channel(target_audio)
         if audio.dim() != 2:
             raise ValueError("MultiResolutionSTFTLoss: expected (B, T) or (B, 1, T) samples, got shape %s" % (tuple(audio.shape),))
         B, T = audio.shape
@@ -717,13 +706,7 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
         Lmax = max(L for L, _, _ in self.resolutions)
         if T <= Lmax // 2:
             raise ValueError("MultiResolutionSTFTLoss: signal of %d samples is too short to reflect-pad by %d" % (T, Lmax // 2))
-        lens = [T] * B
-        if lengths is not None:
-            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-            if len(lens) != B:
-                raise ValueError("MultiResolutionSTFTLoss: %d lengths for a batch of %d" % (len(lens), B))
-            if min(lens) < 1 or max(lens) > T:
-                raise ValueError("MultiResolutionSTFTLoss: lengths must lie in [1, %d], got %s" % (T, lens))
+        lens = _lengths(lengths, B, T, "MultiResolutionSTFTLoss: ", full=T)
         return _MultiResolutionSTFTLoss.apply(self, audio, target_audio, lens, precision)
 
 
@@ -742,15 +725,8 @@ class _MultiResolutionSTFTLoss(torch.autograd.Function):
         cnt_dev = torch.tensor(cnts, dtype=torch.int32).to(dev)
         specs, offs, counts = [], [0], []
         for r, st in enumerate(mod.stfts):
-            L, hop, F = st.filter_length, st.hop_length, st.cutoff
-            n = T // hop + 1
-            ldo = (T + L + 3) // 4 * 4
-            padded = torch.empty(2 * B, ldo, dtype=torch.float32, device=dev)
-            nv.reflect_pad(x, padded[:B], L // 2)
-            nv.reflect_pad(y, padded[B:], L // 2)
-            spec = torch.empty(2 * B * n, 2 * F, dtype=torch.float32, device=dev)       # rows of x, then rows of y
-            frames0 = padded.as_strided((n, L), (hop, 1))
-            nv.gemm(spec[:n], frames0, st.forward_basis.view(2 * F, L), batch=2 * B, strides=(ldo, 0, n * 2 * F))
+            F = st.cutoff
+            spec, n = st.frame_spectra([x, y], st.forward_basis.view(2 * F, st.filter_length), 2 * F)   # rows of x, then rows of y
             specs.append(spec)
             offs.append(offs[-1] + nv.stft_loss_slots(B * n, F))
             counts.append(F * sum(cnts[r]))
@@ -770,10 +746,7 @@ class _MultiResolutionSTFTLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.kept is None:
-            raise RuntimeError("MultiResolutionSTFTLoss: backward was already run; the kept state is freed by the first one")
-        specs, cnt_dev, coef = ctx.kept
-        ctx.kept = None
+        specs, cnt_dev, coef = _take_kept(ctx, "MultiResolutionSTFTLoss")
         mod, (B, T) = ctx.mod, ctx.y_shape
         dev = coef.device
         f32 = dict(dtype=torch.float32, device=dev)
@@ -781,15 +754,11 @@ class _MultiResolutionSTFTLoss(torch.autograd.Function):
         R = len(mod.stfts)
         parts = torch.empty(R, B, T, **f32)
         for r, st in enumerate(mod.stfts):
-            L, hop, F = st.filter_length, st.hop_length, st.cutoff
-            tab = st.bwd_tables(dev)
             rows = specs[r].shape[0] // 2
-            d_spec = torch.empty(rows, tab["Kp"], **f32)
-            nv.stft_loss_bwd(specs[r][:rows], specs[r][rows:], cnt_dev[r], coef[r], g, rows // B, F, mod.eps, d_spec)
+            d_spec = torch.empty(rows, st.bwd_tables(dev)["Kp"], **f32)
+            nv.stft_loss_bwd(specs[r][:rows], specs[r][rows:], cnt_dev[r], coef[r], g, rows // B, st.cutoff, mod.eps, d_spec)
             specs[r] = None
-            d_frames = torch.empty(rows, L, **f32)
-            nv.gemm(d_frames, d_spec, tab["fbt"], fast=ctx.fast)
-            nv.stft_frames_fold(d_frames, parts[r], hop, L // 2)
+            st.spectrum_backward(d_spec, B, T, ctx.fast, out=parts[r])
         if R == 1:
             d_y = parts[0]
         else:

@@ -34,7 +34,7 @@ __global__ void __launch_bounds__(256) magnitude_kernel(const float* __restrict_
     float v = 0.0f;
     if (f < F) {
         const float re = spec[r * lds + f], im = spec[r * lds + F + f];
-        v = sqrtf(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)));
+        v = sqrtf(t2_power(re, im));
     }
     mag[r * ldm + f] = v;
 }

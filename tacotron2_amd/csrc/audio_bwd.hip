@@ -5,14 +5,15 @@
 //   mel_log_bwd:        d_mel[r][m] = d_out[b][m][j] / mel[r][m] where mel >= clip (torch's clamp(min=) rule: the gradient
 //                       passes at equality), exactly 0 elsewhere; the transpose back to frame rows goes through an LDS tile.
 //   stft_magnitude_bwd: d_re = d_mag re / mag, d_im = d_mag im / mag with mag recomputed by magnitude_kernel's operations in
-//                       their order (the forward's bits); both exactly 0 where mag == 0 (a definition: sqrt has no
-//                       derivative there and torch gives NaN).  Zero on the padding columns of d_spec.
+//                       their order (t2_power of common.h: the forward's bits); both exactly 0 where mag == 0 (a definition:
+//                       sqrt has no derivative there and torch gives NaN).  The d_spec row is t2_dspec_store's.
 //   stft_frames_fold:   overlap-add of the frame gradients and the fold of the reflect padding in one gather: sample t sums, in
 //                       ascending padded position and ascending frame order, every frame entry that covers pad - t, pad + t
 //                       and pad + 2 (T - 1) - t, each position taken when t2_reflect maps it onto t.  No d_padded buffer.
 //   mel_l1_fwd / _bwd:  masked mean |out - target| as per-workgroup partial slots (t2amd_wg_partial_sum_f32 adds them in
 //                       order) and sign(out - target) g / count inside the mask, exactly 0 outside.
 // No atomics anywhere: every output element has one writer and every sum a fixed order, so two calls give the same bits.
+// An output whose byte range meets an input's is refused (t2_overlap), not only one that starts where an input starts.
 // No MFMA and no LDS-DMA here, so the CPU suite runs this very source on the host stand-in (tests/hip_emu).
 //
 // Access widths.  Rows whose stride is a multiple of 4 floats are read and written 16 bytes per lane: mel rows (n_mel = 80),
@@ -23,9 +24,6 @@
 
 #define AB_TJ 64                        /* frames per mel_log_bwd tile */
 #define AB_TM 16                        /* mel channels per mel_log_bwd tile */
-
-__device__ __forceinline__ float4 ab_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void ab_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 // ---- log-compress ------------------------------------------------------------------------------------------------------
 // A workgroup owns AB_TJ frames x AB_TM channels of utterance b: reads d_out along the frames (its fast index), writes d_mel
@@ -49,13 +47,13 @@ __global__ void __launch_bounds__(256) mel_log_bwd_kernel(const float* __restric
     if (j < n && m < n_mel) {
         const long long r = (long long)b * n + j;
         if (vec && m + 3 < n_mel) {
-            const float4 v = ab_ld4(mel + r * ld + m);
+            const float4 v = t2_ld4(mel + r * ld + m);
             float4 o;
             o.x = v.x >= clip ? tile[4 * q + 0][jj] / v.x : 0.0f;
             o.y = v.y >= clip ? tile[4 * q + 1][jj] / v.y : 0.0f;
             o.z = v.z >= clip ? tile[4 * q + 2][jj] / v.z : 0.0f;
             o.w = v.w >= clip ? tile[4 * q + 3][jj] / v.w : 0.0f;
-            ab_st4(d_mel + r * ldd + m, o);
+            t2_st4(d_mel + r * ldd + m, o);
         } else {
             for (int e = 0; e < 4 && m + e < n_mel; ++e) {
                 const float v = mel[r * ld + m + e];
@@ -72,7 +70,9 @@ extern "C" int t2amd_mel_log_bwd_f32(const float* d_out, const float* mel, long 
                "mel_log_bwd: bad dims");
     T2_REQUIRE((long long)B * n <= T2_MAX_ROWS, "mel_log_bwd: at most 2^31 - 256 frame rows");
     T2_REQUIRE(clip > 0.0f, "mel_log_bwd: clip must be positive");
-    T2_REQUIRE(d_mel != mel && d_mel != d_out, "mel_log_bwd: d_mel must not be one of the inputs");
+    const long long R = (long long)B * n, d_bytes = ((R - 1) * ldd + n_mel) * 4;
+    T2_REQUIRE(!t2_overlap(d_mel, d_bytes, mel, ((R - 1) * ld + n_mel) * 4) && !t2_overlap(d_mel, d_bytes, d_out, R * n_mel * 4),
+               "mel_log_bwd: d_mel must not be one of the inputs");
     const int vec = ld % 4 == 0 && ldd % 4 == 0 && t2_aligned16(mel) && t2_aligned16(d_mel);
     dim3 grid(t2_cdiv(n, AB_TJ), t2_cdiv(n_mel, AB_TM), B);
     T2_LAUNCH(mel_log_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, d_out, mel, ld, d_mel, ldd, n, n_mel, clip, vec);
@@ -81,8 +81,7 @@ extern "C" int t2amd_mel_log_bwd_f32(const float* d_out, const float* mel, long 
 }
 
 // ---- magnitude ---------------------------------------------------------------------------------------------------------
-// Lane = bin f of row r: d_spec[r] = [d_re (F) | d_im (F) | 0 (Kp - 2F)], spec's own column layout at the row stride the
-// next product wants.  Thread f also writes the padding columns 2F + f, 3F + f, ... below Kp.
+// Lane = bin f of row r; the row of d_spec is t2_dspec_store's (common.h).
 __global__ void __launch_bounds__(256) magnitude_bwd_kernel(const float* __restrict__ d_mag, long long ldm,
                                                             const float* __restrict__ spec, long long lds,
                                                             float* __restrict__ d_spec, long long ldd, long long rows, int F,
@@ -92,29 +91,28 @@ __global__ void __launch_bounds__(256) magnitude_bwd_kernel(const float* __restr
     const long long r = i / F;
     const int f = (int)(i - r * F);
     const float re = spec[r * lds + f], im = spec[r * lds + F + f];
-    const float mag = sqrtf(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)));       // magnitude_kernel's own arithmetic
+    const float mag = sqrtf(t2_power(re, im));                          // magnitude_kernel's own arithmetic
     float dre = 0.0f, dim = 0.0f;
     if (mag != 0.0f) {
         const float g = d_mag[r * ldm + f] / mag;
         dre = __fmul_rn(g, re);
         dim = __fmul_rn(g, im);
     }
-    d_spec[r * ldd + f] = dre;
-    d_spec[r * ldd + F + f] = dim;
-    for (int c = 2 * F + f; c < Kp; c += F) d_spec[r * ldd + c] = 0.0f;
+    t2_dspec_store(d_spec, r * ldd, f, F, Kp, dre, dim);
 }
 
 extern "C" int t2amd_stft_magnitude_bwd_f32(const float* d_mag, long long ldm, const float* spec, long long lds, float* d_spec,
                                             long long ldd, long long rows, int F, int Kp, void* stream) {
     T2_REQUIRE(d_mag && spec && d_spec, "stft_magnitude_bwd: null operand");
     T2_REQUIRE(rows > 0 && rows <= T2_MAX_ROWS && F > 0 && F <= 65536, "stft_magnitude_bwd: bad dims (at most 2^31 - 256 rows)");
-    T2_REQUIRE(Kp >= 2 * F && Kp <= 2 * F + 65536, "stft_magnitude_bwd: d_spec rows hold 2 F values and the padding columns");
-    T2_REQUIRE(ldm >= F && lds >= 2 * (long long)F && ldd >= Kp, "stft_magnitude_bwd: row too short");
-    T2_REQUIRE(d_spec != spec && d_spec != d_mag, "stft_magnitude_bwd: d_spec must not be one of the inputs");
-    const long long blocks = (rows * F + 255) / 256;
-    T2_REQUIRE(blocks <= 0x7fffffffLL, "stft_magnitude_bwd: too many elements for one launch");
-    T2_LAUNCH(magnitude_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_mag, ldm, spec, lds, d_spec, ldd,
-              rows, F, Kp);
+    T2_REQUIRE(ldm >= F && lds >= 2 * (long long)F, "stft_magnitude_bwd: row too short");
+    unsigned blocks;
+    T2_PROPAGATE(t2_dspec_blocks("stft_magnitude_bwd", rows, F, Kp, ldd, &blocks));
+    const long long d_bytes = ((rows - 1) * ldd + Kp) * 4;
+    T2_REQUIRE(!t2_overlap(d_spec, d_bytes, spec, ((rows - 1) * lds + 2 * (long long)F) * 4) &&
+                   !t2_overlap(d_spec, d_bytes, d_mag, ((rows - 1) * ldm + F) * 4),
+               "stft_magnitude_bwd: d_spec must not be one of the inputs");
+    T2_LAUNCH(magnitude_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_mag, ldm, spec, lds, d_spec, ldd, rows, F, Kp);
     T2_LAUNCH_CHECK();
     return T2AMD_OK;
 }
@@ -155,7 +153,7 @@ __global__ void __launch_bounds__(256) frames_fold_kernel(const float* __restric
         if (q - L + 1 <= 0) j0 = 0;
         if (j1 > n - 1) j1 = n - 1;
         for (long long j = j0; j <= j1; ++j) {
-            const float4 v = ab_ld4(rows + j * ldf + (q - j * hop));
+            const float4 v = t2_ld4(rows + j * ldf + (q - j * hop));
             acc[0] += v.x;
             acc[1] += v.y;
             acc[2] += v.z;
@@ -173,7 +171,7 @@ __global__ void __launch_bounds__(256) frames_fold_kernel(const float* __restric
     }
     float* o = d_y + b * ldy + t0;
     if (vec_out && t0 + 3 < T) {
-        ab_st4(o, make_float4(acc[0], acc[1], acc[2], acc[3]));
+        t2_st4(o, make_float4(acc[0], acc[1], acc[2], acc[3]));
     } else {
         for (int e = 0; e < 4 && t0 + e < T; ++e) o[e] = acc[e];
     }
@@ -203,11 +201,7 @@ extern "C" int t2amd_stft_frames_fold_f32(const float* d_frames, long long ldf, 
 // out (B, n_mel, n), target (B, n_mel, N), N <= n; utterance b counts its first lens[b] frames (lens NULL: N).  A workgroup
 // owns `rpb` consecutive (b, m) rows: a thread adds its frames in ascending order in float64, the wave butterfly and the four
 // wave sums follow in a fixed order, and the workgroup stores sum / count as its partial slot.
-__device__ __forceinline__ int ab_len(const int* lens, int b, int N) {
-    int len = lens ? lens[b] : N;
-    if (len > N) len = N;
-    return len < 0 ? 0 : len;
-}
+__device__ __forceinline__ int ab_len(const int* lens, int b, int N) { return t2_clamp_count(lens ? lens[b] : N, N); }
 
 __global__ void __launch_bounds__(256) mel_l1_fwd_kernel(const float* __restrict__ out, const float* __restrict__ target,
                                                          const int* __restrict__ lens, int n_mel, int n, int N, long long RW,
@@ -226,7 +220,7 @@ __global__ void __launch_bounds__(256) mel_l1_fwd_kernel(const float* __restrict
     for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
     if ((tid & 63) == 0) wsum[tid >> 6] = acc;
     __syncthreads();
-    if (tid == 0) partial[blockIdx.x] = (float)((((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]) / count);
+    if (tid == 0) partial[blockIdx.x] = (float)(t2_block_total_f64(wsum) / count);
 }
 
 extern "C" int t2amd_mel_l1_rows_per_slot(int n) {
@@ -274,8 +268,9 @@ extern "C" int t2amd_mel_l1_bwd_f32(const float* out, const float* target, const
     T2_REQUIRE(B > 0 && B <= 65535 && n_mel > 0 && n_mel <= 65535 && n > 0 && N > 0, "mel_l1_bwd: bad dims");
     T2_REQUIRE(N <= n, "mel_l1_bwd: the target has more frames than the prediction");
     T2_REQUIRE(count > 0 && count <= (long long)B * n_mel * N, "mel_l1_bwd: count must be n_mel times the frames inside the mask");
-    T2_REQUIRE(d_out != out && d_out != target, "mel_l1_bwd: d_out must not be one of the inputs");
     const long long total = (long long)B * n_mel * n, blocks = (total + 255) / 256;
+    T2_REQUIRE(!t2_overlap(d_out, total * 4, out, total * 4) && !t2_overlap(d_out, total * 4, target, (long long)B * n_mel * N * 4),
+               "mel_l1_bwd: d_out must not be one of the inputs");
     T2_REQUIRE(blocks <= 0x7fffffffLL, "mel_l1_bwd: too many elements for one launch");
     T2_LAUNCH(mel_l1_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, target, lens, g, n_mel, n, N, total,
               (float)count, d_out);

@@ -206,3 +206,67 @@ static __host__ __device__ __forceinline__ long long t2_reflect(long long i, lon
 
 // The most rows of a packed row image (HiFi-GAN, Vocos): 2^31 - 256, so that grid.x = rows / 128 and 32-bit row sums hold
 #define T2_MAX_ROWS 2147483392LL
+
+// ---- row-kernel helpers of the audio losses and the vocoders ------------------------------------------------------------------
+// Plain C++ and __shfl_xor only (no DPP, no builtins): tests/hip_emu compiles them with the kernels that call them.  Each is the
+// one statement of something a backward kernel must repeat bit for bit from its forward, or of a layout two kernels share.
+
+// re^2 + im^2 of a spectrum bin, three roundings: the magnitude of audio.hip and vocoder.hip, recomputed by audio_bwd.hip and
+// stft_loss.hip ("the forward's bits")
+__device__ __forceinline__ float t2_power(float re, float im) { return __fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)); }
+
+// sum over the wave as a xor butterfly 32, 16, .. 1: the same bits in every lane.  NOT wave_reduce_sum: its DPP steps associate
+// in another order.  (float clients only so far: on the float64 sums below it moved instructions.)
+template <class T>
+__device__ __forceinline__ T t2_wave_sum(T v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// The fixed-order float64 sum of a 256-thread workgroup (stft_loss_fwd_kernel, stft_loss_finish_kernel, mel_l1_fwd_kernel): the
+// xor butterfly in every wave, the four wave sums into LDS, a barrier, then this combine in thread 0.  The first three steps stay
+// written out in the kernels: as a helper they made the compiler schedule those kernels differently.
+__device__ __forceinline__ double t2_block_total_f64(const double (&w)[4]) { return ((w[0] + w[1]) + w[2]) + w[3]; }
+
+// a per-utterance count clamped into [0, n]
+__device__ __forceinline__ int t2_clamp_count(int c, int n) {
+    if (c > n) c = n;
+    return c < 0 ? 0 : c;
+}
+
+__device__ __forceinline__ float4 t2_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void t2_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+
+// The d_spec row of the spectral backward, [d_re (F) | d_im (F) | 0 (Kp - 2F)]: spec's own column layout at the row stride the
+// product d_frames = d_spec . forward_basis wants.  The lane of bin f stores its two values and the padding columns 2F + f,
+// 3F + f, ... below Kp; row0 = the row's first float.  Written by magnitude_bwd_kernel (audio_bwd.hip) and stft_loss_bwd_kernel (stft_loss.hip), one lane per
+// bin, rows * F lanes in workgroups of 256.
+__device__ __forceinline__ void t2_dspec_store(float* d_spec, long long row0, int f, int F, int Kp, float dre, float dim) {
+    d_spec[row0 + f] = dre;
+    d_spec[row0 + F + f] = dim;
+    for (int c = 2 * F + f; c < Kp; c += F) d_spec[row0 + c] = 0.0f;
+}
+
+// host side of the same: the checks of Kp and ldd and the workgroups of a launch over rows * F lanes (rows > 0 and
+// 0 < F <= 65536 already checked); `who` is the entry point's prefix of the error text
+static inline int t2_dspec_blocks(const char* who, long long rows, int F, int Kp, long long ldd, unsigned* blocks) {
+    char msg[160];
+    const long long nb = (rows * F + 255) / 256;
+    const char* what = !(Kp >= 2 * F && Kp <= 2 * F + 65536) ? "d_spec rows hold 2 F values and the padding columns"
+                       : ldd < Kp                            ? "row too short"
+                       : nb > 0x7fffffffLL                   ? "too many elements for one launch"
+                                                             : nullptr;
+    if (what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        T2_FAIL(msg);
+    }
+    *blocks = (unsigned)nb;
+    return T2AMD_OK;
+}
+
+// do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte: the aliasing check of an output against an input
+static inline bool t2_overlap(const void* a, long long a_bytes, const void* b, long long b_bytes) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return pa < pb + (uintptr_t)b_bytes && pb < pa + (uintptr_t)a_bytes;
+}

@@ -8,8 +8,8 @@
 //                     (sc_weight / (R sqrt(A) sqrt(Bn)), 0 where A == 0, and mag_weight / (R C)).  No host read in between.
 //   stft_loss_bwd:    d_m = c_sc (m_x - m_y) + c_mag sign(ln m_x - ln m_y) / m_x, d_re = g d_m re / m_x, d_im = g d_m im / m_x
 //                     where p >= eps (torch's clamp rule: the gradient passes at equality), exactly 0 below and on the frames
-//                     outside the mask; m recomputed by the forward's operations in the forward's order.  d_spec has
-//                     magnitude_bwd_kernel's layout [d_re (F) | d_im (F) | 0 (Kp - 2F)].
+//                     outside the mask; m recomputed by the forward's operations in the forward's order (t2_power, sl_mag).
+//                     The rows of d_spec are t2_dspec_store's (common.h), as magnitude_bwd_kernel's.
 //   stft_loss_sum:    d_y = ((part_0 + part_1) + ...) + part_{R-1}, one writer per sample.
 // No atomics anywhere: every output element has one writer and every sum a fixed order, so two calls give the same bits.
 // No MFMA and no LDS-DMA here, so the CPU suite runs this very source on the host stand-in (tests/hip_emu).
@@ -22,14 +22,7 @@
 #define SL_MAX_RES 8                    /* resolutions of one stft_loss_finish / stft_loss_sum launch */
 #define SL_SLOT_ELEMS 16384             /* about this many bins per partial slot */
 
-__device__ __forceinline__ float sl_power(float re, float im) { return __fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)); }
 __device__ __forceinline__ float sl_mag(float p, float eps) { return sqrtf(fmaxf(p, eps)); }
-
-__device__ __forceinline__ int sl_count(const int* cnt, int b, int n) {
-    int c = cnt[b];
-    if (c > n) c = n;
-    return c < 0 ? 0 : c;
-}
 
 // ---- forward sums ------------------------------------------------------------------------------------------------------
 // A workgroup owns `rpb` consecutive frame rows: a thread adds its bins (f = tid, tid + 256, ...) row after row in float64, the
@@ -46,12 +39,12 @@ __global__ void __launch_bounds__(256) stft_loss_fwd_kernel(const float* __restr
         const long long row = row0 + rr;
         if (row >= rows) break;
         const long long b = row / n;
-        if ((int)(row - b * n) >= sl_count(cnt, (int)b, n)) continue;
+        if ((int)(row - b * n) >= t2_clamp_count(cnt[(int)b], n)) continue;
         const float* px = spec_x + row * ldx;
         const float* py = spec_y + row * ldy;
         for (int f = tid; f < F; f += 256) {
-            const float mx = sl_mag(sl_power(px[f], px[F + f]), eps);
-            const float my = sl_mag(sl_power(py[f], py[F + f]), eps);
+            const float mx = sl_mag(t2_power(px[f], px[F + f]), eps);
+            const float my = sl_mag(t2_power(py[f], py[F + f]), eps);
             const double d = (double)my - (double)mx;
             a += d * d;
             bn += (double)my * (double)my;
@@ -72,18 +65,13 @@ __global__ void __launch_bounds__(256) stft_loss_fwd_kernel(const float* __restr
     __syncthreads();
     if (tid == 0) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) slots[3 * (long long)blockIdx.x + k] = ((wsum[k][0] + wsum[k][1]) + wsum[k][2]) + wsum[k][3];
+        for (int k = 0; k < 3; ++k) slots[3 * (long long)blockIdx.x + k] = t2_block_total_f64(wsum[k]);
     }
 }
 
 extern "C" int t2amd_stft_loss_rows_per_slot(int F) {
     if (F < 1) F = 1;
     return F >= SL_SLOT_ELEMS ? 1 : (SL_SLOT_ELEMS + F - 1) / F;
-}
-
-static bool sl_overlap(const void* a, long long a_bytes, const void* b, long long b_bytes) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + (uintptr_t)b_bytes && pb < pa + (uintptr_t)a_bytes;
 }
 
 extern "C" int t2amd_stft_loss_fwd_f32(const float* spec_x, long long ldx, const float* spec_y, long long ldy, const int* cnt,
@@ -98,8 +86,8 @@ extern "C" int t2amd_stft_loss_fwd_f32(const float* spec_x, long long ldx, const
     const long long nslots = (rows + rpb - 1) / rpb;
     T2_REQUIRE(slot_doubles >= 3 * nslots, "stft_loss_fwd: the slot buffer is shorter than its 3 doubles per slot");
     T2_REQUIRE((reinterpret_cast<uintptr_t>(slots) & 7u) == 0, "stft_loss_fwd: the slot buffer is misaligned");
-    T2_REQUIRE(!sl_overlap(slots, 3 * nslots * 8, spec_x, ((rows - 1) * ldx + 2 * (long long)F) * 4) &&
-                   !sl_overlap(slots, 3 * nslots * 8, spec_y, ((rows - 1) * ldy + 2 * (long long)F) * 4),
+    T2_REQUIRE(!t2_overlap(slots, 3 * nslots * 8, spec_x, ((rows - 1) * ldx + 2 * (long long)F) * 4) &&
+                   !t2_overlap(slots, 3 * nslots * 8, spec_y, ((rows - 1) * ldy + 2 * (long long)F) * 4),
                "stft_loss_fwd: the slot buffer must not be one of the inputs");
     T2_LAUNCH(stft_loss_fwd_kernel, dim3((unsigned)nslots), dim3(256), 0, (hipStream_t)stream, spec_x, ldx, spec_y, ldy, cnt, n, F,
               rows, rpb, eps, slots);
@@ -141,9 +129,7 @@ __global__ void __launch_bounds__(256) stft_loss_finish_kernel(const double* __r
         }
         __syncthreads();
         if (tid == 0) {
-            const double A = ((wsum[0][0] + wsum[0][1]) + wsum[0][2]) + wsum[0][3];
-            const double Bn = ((wsum[1][0] + wsum[1][1]) + wsum[1][2]) + wsum[1][3];
-            const double Lm = ((wsum[2][0] + wsum[2][1]) + wsum[2][2]) + wsum[2][3];
+            const double A = t2_block_total_f64(wsum[0]), Bn = t2_block_total_f64(wsum[1]), Lm = t2_block_total_f64(wsum[2]);
             const double ra = sqrt(A), rb = sqrt(Bn);
             const double sc = A == 0.0 ? 0.0 : ra / rb;                 // a definition: no gradient and no value where A == 0
             const double lmr = Lm / plan.count[r];
@@ -176,8 +162,8 @@ extern "C" int t2amd_stft_loss_finish_f64(const double* slots, long long slot_do
     for (int r = 0; r <= R; ++r) plan.off[r] = slot_off[r];
     T2_REQUIRE(slot_off[R] <= slot_doubles / 3, "stft_loss_finish: the slot buffer is shorter than its 3 doubles per slot");
     T2_REQUIRE(loss != terms && loss != coef && terms != coef, "stft_loss_finish: the outputs must be distinct");
-    T2_REQUIRE(!sl_overlap(slots, slot_doubles * 8, loss, 4) && !sl_overlap(slots, slot_doubles * 8, terms, 8LL * R) &&
-                   !sl_overlap(slots, slot_doubles * 8, coef, 8LL * R),
+    T2_REQUIRE(!t2_overlap(slots, slot_doubles * 8, loss, 4) && !t2_overlap(slots, slot_doubles * 8, terms, 8LL * R) &&
+                   !t2_overlap(slots, slot_doubles * 8, coef, 8LL * R),
                "stft_loss_finish: an output must not lie in the slot buffer");
     T2_LAUNCH(stft_loss_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, slots, plan, R, sc_weight, mag_weight, loss, terms,
               coef);
@@ -186,9 +172,8 @@ extern "C" int t2amd_stft_loss_finish_f64(const double* slots, long long slot_do
 }
 
 // ---- backward ----------------------------------------------------------------------------------------------------------
-// Lane = bin f of row r, as magnitude_bwd_kernel: d_spec[r] = [d_re (F) | d_im (F) | 0 (Kp - 2F)]; thread f also writes the
-// padding columns 2F + f, 3F + f, ... below Kp.  coef = this resolution's (c_sc, c_mag), g = the upstream scalar, both read on
-// the device.
+// Lane = bin f of row r, as magnitude_bwd_kernel; the row of d_spec is t2_dspec_store's (common.h).  coef = this resolution's
+// (c_sc, c_mag), g = the upstream scalar, both read on the device.
 __global__ void __launch_bounds__(256) stft_loss_bwd_kernel(const float* __restrict__ spec_x, long long ldx,
                                                             const float* __restrict__ spec_y, long long ldy,
                                                             const int* __restrict__ cnt, const float* __restrict__ coef,
@@ -200,12 +185,12 @@ __global__ void __launch_bounds__(256) stft_loss_bwd_kernel(const float* __restr
     const int f = (int)(i - r * F);
     const long long b = r / n;
     float dre = 0.0f, dim = 0.0f;
-    if ((int)(r - b * n) < sl_count(cnt, (int)b, n)) {
+    if ((int)(r - b * n) < t2_clamp_count(cnt[(int)b], n)) {
         const float re = spec_x[r * ldx + f], im = spec_x[r * ldx + F + f];
-        const float p = sl_power(re, im);
+        const float p = t2_power(re, im);
         if (p >= eps) {
             const float mx = sl_mag(p, eps);
-            const float my = sl_mag(sl_power(spec_y[r * ldy + f], spec_y[r * ldy + F + f]), eps);
+            const float my = sl_mag(t2_power(spec_y[r * ldy + f], spec_y[r * ldy + F + f]), eps);
             const float d = logf(mx) - logf(my);
             const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
             const float up = g[0];
@@ -215,9 +200,7 @@ __global__ void __launch_bounds__(256) stft_loss_bwd_kernel(const float* __restr
             dim = __fmul_rn(q, im);
         }
     }
-    d_spec[r * ldd + f] = dre;
-    d_spec[r * ldd + F + f] = dim;
-    for (int c = 2 * F + f; c < Kp; c += F) d_spec[r * ldd + c] = 0.0f;
+    t2_dspec_store(d_spec, r * ldd, f, F, Kp, dre, dim);
 }
 
 extern "C" int t2amd_stft_loss_bwd_f32(const float* spec_x, long long ldx, const float* spec_y, long long ldy, const int* cnt,
@@ -226,20 +209,19 @@ extern "C" int t2amd_stft_loss_bwd_f32(const float* spec_x, long long ldx, const
     T2_REQUIRE(spec_x && spec_y && cnt && coef && g && d_spec, "stft_loss_bwd: null operand");
     T2_REQUIRE(B > 0 && B <= 65535 && n > 0 && F > 0 && F <= 65536, "stft_loss_bwd: bad dims");
     T2_REQUIRE((long long)B * n <= T2_MAX_ROWS, "stft_loss_bwd: at most 2^31 - 256 frame rows");
-    T2_REQUIRE(Kp >= 2 * F && Kp <= 2 * F + 65536, "stft_loss_bwd: d_spec rows hold 2 F values and the padding columns");
-    T2_REQUIRE(ldx >= 2 * (long long)F && ldy >= 2 * (long long)F && ldd >= Kp, "stft_loss_bwd: row too short");
+    T2_REQUIRE(ldx >= 2 * (long long)F && ldy >= 2 * (long long)F, "stft_loss_bwd: row too short");
     T2_REQUIRE(eps > 0.0f, "stft_loss_bwd: eps must be positive");
     const long long rows = (long long)B * n;
+    unsigned blocks;
+    T2_PROPAGATE(t2_dspec_blocks("stft_loss_bwd", rows, F, Kp, ldd, &blocks));
     T2_REQUIRE(d_floats >= (rows - 1) * ldd + Kp, "stft_loss_bwd: d_spec is shorter than its B n rows of Kp");
     const long long d_bytes = ((rows - 1) * ldd + Kp) * 4;
-    T2_REQUIRE(!sl_overlap(d_spec, d_bytes, spec_x, ((rows - 1) * ldx + 2 * (long long)F) * 4) &&
-                   !sl_overlap(d_spec, d_bytes, spec_y, ((rows - 1) * ldy + 2 * (long long)F) * 4) &&
-                   !sl_overlap(d_spec, d_bytes, coef, 8) && !sl_overlap(d_spec, d_bytes, g, 4),
+    T2_REQUIRE(!t2_overlap(d_spec, d_bytes, spec_x, ((rows - 1) * ldx + 2 * (long long)F) * 4) &&
+                   !t2_overlap(d_spec, d_bytes, spec_y, ((rows - 1) * ldy + 2 * (long long)F) * 4) &&
+                   !t2_overlap(d_spec, d_bytes, coef, 8) && !t2_overlap(d_spec, d_bytes, g, 4),
                "stft_loss_bwd: d_spec must not be one of the inputs");
-    const long long blocks = (rows * F + 255) / 256;
-    T2_REQUIRE(blocks <= 0x7fffffffLL, "stft_loss_bwd: too many elements for one launch");
-    T2_LAUNCH(stft_loss_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, spec_x, ldx, spec_y, ldy, cnt, coef, g,
-              n, rows, F, Kp, eps, d_spec, ldd);
+    T2_LAUNCH(stft_loss_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, spec_x, ldx, spec_y, ldy, cnt, coef, g, n, rows,
+              F, Kp, eps, d_spec, ldd);
     T2_LAUNCH_CHECK();
     return T2AMD_OK;
 }
@@ -260,7 +242,7 @@ extern "C" int t2amd_stft_loss_sum_f32(const float* parts, long long stride, lon
     T2_REQUIRE(R >= 1 && R <= SL_MAX_RES, "stft_loss_sum: 1 to 8 parts");
     T2_REQUIRE(total > 0 && stride >= total, "stft_loss_sum: bad dims");
     T2_REQUIRE(part_floats >= (R - 1) * stride + total, "stft_loss_sum: parts is shorter than its R images");
-    T2_REQUIRE(!sl_overlap(out, total * 4, parts, ((R - 1) * stride + total) * 4), "stft_loss_sum: out must not lie in parts");
+    T2_REQUIRE(!t2_overlap(out, total * 4, parts, ((R - 1) * stride + total) * 4), "stft_loss_sum: out must not lie in parts");
     const long long blocks = (total + 255) / 256;
     T2_REQUIRE(blocks <= 0x7fffffffLL, "stft_loss_sum: too many elements for one launch");
     T2_LAUNCH(stft_loss_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, parts, stride, R, total, out);

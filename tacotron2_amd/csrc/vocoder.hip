@@ -99,7 +99,7 @@ __global__ void __launch_bounds__(256) gl_project_kernel(const float* __restrict
         if (f < F && r - row0[b] < nb[b]) {
             const t2_f2 z = *reinterpret_cast<const t2_f2*>(spec + r * lds + 2 * f);
             const float m = S[r * ldS + f];
-            const float a = sqrtf(__fadd_rn(__fmul_rn(z.x, z.x), __fmul_rn(z.y, z.y)));
+            const float a = sqrtf(t2_power(z.x, z.y));
             if (a > 0.0f) {
                 o.x = m * (z.x / a);
                 o.y = m * (z.y / a);
@@ -152,7 +152,7 @@ __global__ void __launch_bounds__(256) gl_polar_kernel(const float* __restrict__
         const long long b = t / F;
         const long long f = t - b * F;
         const t2_f2 z = *reinterpret_cast<const t2_f2*>(spec + (b * n + j) * lds + 2 * f);
-        if (mag) mag[i] = sqrtf(__fadd_rn(__fmul_rn(z.x, z.x), __fmul_rn(z.y, z.y)));
+        if (mag) mag[i] = sqrtf(t2_power(z.x, z.y));
         if (phase) phase[i] = atan2f(z.y, z.x);
     }
 }

@@ -20,15 +20,6 @@
 
 extern "C" int t2amd_vc_bwd_slot_rows() { return VCB_WAVE_ROWS; }
 
-__device__ __forceinline__ float vcb_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
-__device__ __forceinline__ float4 vcb_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void vcb_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
 // ---- overlap-add -----------------------------------------------------------------------------------------------------
 // Row p of utterance b = rowb0[p], frame j = rowr0[p]: sample t of the frame is position s = j hop + t of the untrimmed
 // overlap-add, output sample s - trim.  env is summed over the covering frames in ascending order, as vc_ola_kernel does.
@@ -57,7 +48,7 @@ __global__ __launch_bounds__(256) void vc_ola_bwd_kernel(const float* d_audio, l
             o[e] = d_audio[(long long)b * T + ts] / env;
         }
     }
-    vcb_st4(d_frames + p * ldf + t0, make_float4(o[0], o[1], o[2], o[3]));
+    t2_st4(d_frames + p * ldf + t0, make_float4(o[0], o[1], o[2], o[3]));
 }
 
 extern "C" int t2amd_vc_ola_bwd_f32(const float* d_audio, long long T, long long a_floats, const float* wsq, const int* utt, int B,
@@ -142,13 +133,13 @@ __global__ __launch_bounds__(256) void vc_gelu_bwd_kernel(const float* U, long l
     const int c = 4 * (int)(i - p * nq);
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
     if (rowb0[p] >= 0) {
-        const float4 u = vcb_ld4(U + p * ldu + c), d = vcb_ld4(dH + p * ldh + c);
+        const float4 u = t2_ld4(U + p * ldu + c), d = t2_ld4(dH + p * ldh + c);
         o.x = d.x * vcb_gelu_grad(u.x);
         o.y = d.y * vcb_gelu_grad(u.y);
         o.z = d.z * vcb_gelu_grad(u.z);
         o.w = d.w * vcb_gelu_grad(u.w);
     }
-    vcb_st4(dH + p * ldh + c, o);
+    t2_st4(dH + p * ldh + c, o);
 }
 
 extern "C" int t2amd_vc_gelu_bwd_f32(const float* U, long long u_floats, long long ldu, long long P, int I, const int* rowb0,
@@ -175,23 +166,23 @@ __global__ __launch_bounds__(64 * VCB_WAVES) void vc_gamma_bwd_kernel(const floa
     if (p0 >= P) return;
     const int nq = D >> 2;
     for (int q = lane; q < nq; q += 64) {
-        const float4 g = vcb_ld4(gamma + 4 * q);
+        const float4 g = t2_ld4(gamma + 4 * q);
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int j = 0; j < VCB_WAVE_ROWS; ++j) {
             const long long p = p0 + j;
             if (p >= P) break;
             float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
             if (rowb0[p] >= 0) {
-                const float4 d = vcb_ld4(dX + p * lddx + 4 * q), y = vcb_ld4(Y2 + p * ldy + 4 * q);
+                const float4 d = t2_ld4(dX + p * lddx + 4 * q), y = t2_ld4(Y2 + p * ldy + 4 * q);
                 acc.x = fmaf(d.x, y.x, acc.x);
                 acc.y = fmaf(d.y, y.y, acc.y);
                 acc.z = fmaf(d.z, y.z, acc.z);
                 acc.w = fmaf(d.w, y.w, acc.w);
                 o = make_float4(g.x * d.x, g.y * d.y, g.z * d.z, g.w * d.w);
             }
-            vcb_st4(Y2 + p * ldy + 4 * q, o);
+            t2_st4(Y2 + p * ldy + 4 * q, o);
         }
-        vcb_st4(partial + slot * D + 4 * q, acc);
+        t2_st4(partial + slot * D + 4 * q, acc);
     }
 }
 
@@ -244,14 +235,14 @@ __global__ __launch_bounds__(64 * VCB_WAVES) void vc_ln_bwd_kernel(const float* 
             float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
             if (real && q < nq) {
                 if (taps == 0) {
-                    a = vcb_ld4(X + p * ldx + 4 * q);
+                    a = t2_ld4(X + p * ldx + 4 * q);
                 } else {
-                    a = vcb_ld4(cb + 4 * q);
+                    a = t2_ld4(cb + 4 * q);
                     for (int t = 0; t < taps; ++t) {
                         const long long src = p + t - half;
                         if (src < 0 || src >= P) continue;
-                        const float4 x = vcb_ld4(X + src * ldx + 4 * q);
-                        const float4 k = vcb_ld4(w + (long long)t * D + 4 * q);
+                        const float4 x = t2_ld4(X + src * ldx + 4 * q);
+                        const float4 k = t2_ld4(w + (long long)t * D + 4 * q);
                         a.x = fmaf(x.x, k.x, a.x);
                         a.y = fmaf(x.y, k.y, a.y);
                         a.z = fmaf(x.z, k.z, a.z);
@@ -262,7 +253,7 @@ __global__ __launch_bounds__(64 * VCB_WAVES) void vc_ln_bwd_kernel(const float* 
             }
             v[i] = a;
         }
-        const float mean = vcb_wave_sum(s) / (float)D;
+        const float mean = t2_wave_sum(s) / (float)D;
         float ss = 0.f;
 #pragma unroll
         for (int i = 0; i < VCB_MAX_D / 256; ++i) {
@@ -275,14 +266,14 @@ __global__ __launch_bounds__(64 * VCB_WAVES) void vc_ln_bwd_kernel(const float* 
                 ss += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
             }
         }
-        const float rstd = 1.0f / sqrtf(vcb_wave_sum(ss) / (float)D + eps);
+        const float rstd = 1.0f / sqrtf(t2_wave_sum(ss) / (float)D + eps);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int i = 0; i < VCB_MAX_D / 256; ++i) {
             const int q = lane + 64 * i;
             wd[i] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (real && q < nq) {
-                const float4 g = vcb_ld4(G + p * ldg + 4 * q), k = vcb_ld4(lw + 4 * q);
+                const float4 g = t2_ld4(G + p * ldg + 4 * q), k = t2_ld4(lw + 4 * q);
                 v[i] = make_float4(v[i].x * rstd, v[i].y * rstd, v[i].z * rstd, v[i].w * rstd);
                 wd[i] = make_float4(g.x * k.x, g.y * k.y, g.z * k.z, g.w * k.w);
                 s1 += (wd[i].x + wd[i].y) + (wd[i].z + wd[i].w);
@@ -297,7 +288,7 @@ __global__ __launch_bounds__(64 * VCB_WAVES) void vc_ln_bwd_kernel(const float* 
                 ab[i].w += g.w;
             }
         }
-        const float m1 = vcb_wave_sum(s1) / (float)D, m2 = vcb_wave_sum(s2) / (float)D;
+        const float m1 = t2_wave_sum(s1) / (float)D, m2 = t2_wave_sum(s2) / (float)D;
 #pragma unroll
         for (int i = 0; i < VCB_MAX_D / 256; ++i) {
             const int q = lane + 64 * i;
@@ -309,15 +300,15 @@ __global__ __launch_bounds__(64 * VCB_WAVES) void vc_ln_bwd_kernel(const float* 
                 o.z = rstd * (wd[i].z - m1 - v[i].z * m2);
                 o.w = rstd * (wd[i].w - m1 - v[i].w * m2);
             }
-            vcb_st4(dZ + p * lddz + 4 * q, o);
+            t2_st4(dZ + p * lddz + 4 * q, o);
         }
     }
 #pragma unroll
     for (int i = 0; i < VCB_MAX_D / 256; ++i) {
         const int q = lane + 64 * i;
         if (q >= nq || p0 >= P) continue;
-        vcb_st4(partial + slot * 2 * D + 4 * q, aw[i]);
-        vcb_st4(partial + slot * 2 * D + D + 4 * q, ab[i]);
+        t2_st4(partial + slot * 2 * D + 4 * q, aw[i]);
+        t2_st4(partial + slot * 2 * D + D + 4 * q, ab[i]);
     }
 }
 
@@ -368,21 +359,21 @@ __global__ __launch_bounds__(64 * VCB_WAVES) void vc_dw_bwd_kernel(const float* 
             if (p >= P) break;
             float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
             if (rowb0[p] >= 0) {
-                if (res) o = vcb_ld4(res + p * ldres + 4 * q);
-                const float4 z = vcb_ld4(dZ + p * lddz + 4 * q);
+                if (res) o = t2_ld4(res + p * ldres + 4 * q);
+                const float4 z = t2_ld4(dZ + p * lddz + 4 * q);
 #pragma unroll
                 for (int t = 0; t < VCB_MAX_TAPS; ++t) {
                     if (t >= taps) continue;
                     const long long sz = p + half - t, sx = p + t - half;
                     if (sz >= 0 && sz < P) {
-                        const float4 zz = vcb_ld4(dZ + sz * lddz + 4 * q), k = vcb_ld4(w + (long long)t * D + 4 * q);
+                        const float4 zz = t2_ld4(dZ + sz * lddz + 4 * q), k = t2_ld4(w + (long long)t * D + 4 * q);
                         o.x = fmaf(k.x, zz.x, o.x);
                         o.y = fmaf(k.y, zz.y, o.y);
                         o.z = fmaf(k.z, zz.z, o.z);
                         o.w = fmaf(k.w, zz.w, o.w);
                     }
                     if (sx >= 0 && sx < P) {
-                        const float4 x = vcb_ld4(X + sx * ldx + 4 * q);
+                        const float4 x = t2_ld4(X + sx * ldx + 4 * q);
                         acc[t].x = fmaf(z.x, x.x, acc[t].x);
                         acc[t].y = fmaf(z.y, x.y, acc[t].y);
                         acc[t].z = fmaf(z.z, x.z, acc[t].z);
@@ -394,12 +385,12 @@ __global__ __launch_bounds__(64 * VCB_WAVES) void vc_dw_bwd_kernel(const float* 
                 acc[VCB_MAX_TAPS].z += z.z;
                 acc[VCB_MAX_TAPS].w += z.w;
             }
-            vcb_st4(dX + p * lddx + 4 * q, o);
+            t2_st4(dX + p * lddx + 4 * q, o);
         }
 #pragma unroll
         for (int t = 0; t < VCB_MAX_TAPS; ++t)
-            if (t < taps) vcb_st4(part + (long long)t * D + 4 * q, acc[t]);
-        vcb_st4(part + (long long)taps * D + 4 * q, acc[VCB_MAX_TAPS]);
+            if (t < taps) t2_st4(part + (long long)t * D + 4 * q, acc[t]);
+        t2_st4(part + (long long)taps * D + 4 * q, acc[VCB_MAX_TAPS]);
     }
 }
 

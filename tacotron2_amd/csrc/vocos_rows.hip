@@ -13,12 +13,6 @@
 #define VC_MAX_TAPS 15
 #define VC_DWLN_ROWS 4                  /* waves (= rows) per workgroup */
 
-__device__ __forceinline__ float vc_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 __global__ __launch_bounds__(64 * VC_DWLN_ROWS) void vc_dwln_kernel(const float* X, long long ldx, long long P, int D,
                                                                     const float* w, const float* cb, int taps, const float* lw,
                                                                     const float* lb, float eps, const int* rowb0, float* out,
@@ -54,7 +48,7 @@ __global__ __launch_bounds__(64 * VC_DWLN_ROWS) void vc_dwln_kernel(const float*
         }
         v[i] = a;
     }
-    const float mean = vc_wave_sum(s) / (float)D;
+    const float mean = t2_wave_sum(s) / (float)D;
     float ss = 0.f;
 #pragma unroll
     for (int i = 0; i < VC_MAX_D / 256; ++i) {
@@ -67,7 +61,7 @@ __global__ __launch_bounds__(64 * VC_DWLN_ROWS) void vc_dwln_kernel(const float*
             ss += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
         }
     }
-    const float rstd = 1.0f / sqrtf(vc_wave_sum(ss) / (float)D + eps);
+    const float rstd = 1.0f / sqrtf(t2_wave_sum(ss) / (float)D + eps);
     if (!inside) return;
 #pragma unroll
     for (int i = 0; i < VC_MAX_D / 256; ++i) {

@@ -23,11 +23,6 @@
 #define WGN_SHORT 4          // rows of at most this many floats: one lane per row
 #define WGN_KEEP 3           // float4 per lane kept in registers
 
-__device__ __forceinline__ float wgn_wave_sum(float s) {
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-    return s;
-}
-
 // the table line that holds work unit u (first[s] <= u < first[s + 1]); n_seg >= 1 and u < n_units
 __device__ __forceinline__ int wgn_find(const long long* __restrict__ table, int n_seg, long long u) {
     int lo = 0, hi = n_seg - 1;
@@ -81,7 +76,7 @@ __global__ void __launch_bounds__(64 * WGN_WAVES) wg_weight_norm_kernel(const lo
     } else if (active && !shortrow) {
         for (long long j = lane; j < len; j += 64) s += v[j] * v[j];
     }
-    s = wgn_wave_sum(s);
+    s = t2_wave_sum(s);
     if (!active) return;
     if (shortrow) {
         if (r >= rows) return;
@@ -156,7 +151,7 @@ __global__ void __launch_bounds__(64 * WGN_WAVES) wg_weight_norm_bwd_kernel(
     } else if (active && !shortrow) {
         for (long long j = lane; j < len; j += 64) s += dw[j] * v[j];
     }
-    s = wgn_wave_sum(s);
+    s = t2_wave_sum(s);
     if (!active) return;
     if (shortrow) {
         if (r >= rows) return;

@@ -247,6 +247,25 @@ def test_entries_reject_bad_arguments(native_lib):
         native.mel_l1_bwd(out, tgt, None, z(1), 8, z(B, n_mel, n))
         _err(native.mel_l1_bwd, out, tgt, None, z(2), 8, z(B, n_mel, n), match="g of 2")
         _err(native.mel_l1_bwd, out, tgt, None, z(1), 8, out, match="must not be one of the inputs")
+        # an output that shares one element with an input is refused (byte ranges, not pointer equality); the neighbour is not
+        buf, k = z(3 * R * n_mel), R * n_mel
+        mel, d_out = buf[:k].view(R, n_mel), buf[2 * k:].view(B, n_mel, n)
+        native.mel_log_bwd(d_out, mel, buf[k:2 * k].view(R, n_mel), 1e-5)
+        _err(native.mel_log_bwd, d_out, mel, buf[k - 1:2 * k - 1].view(R, n_mel), 1e-5, match="must not be one of the inputs")
+        _err(native.mel_log_bwd, d_out, mel, buf[k + 1:2 * k + 1].view(R, n_mel), 1e-5, match="must not be one of the inputs")
+        buf, ks, kd = z(R * (2 * Fb + Kp + 32)), R * 2 * Fb, R * Kp
+        spec, d_mag = buf[:ks].view(R, 2 * Fb), buf[ks + kd:].view(R, 32)
+        native.stft_magnitude_bwd(d_mag, spec, buf[ks:ks + kd].view(R, Kp), Fb)
+        _err(native.stft_magnitude_bwd, d_mag, spec, buf[ks - 1:ks + kd - 1].view(R, Kp), Fb, match="must not be one of the inputs")
+        # d_mag's last row ends after F of its 32 floats: the first overlapping d_spec reaches into the element F - 1 of that row
+        native.stft_magnitude_bwd(buf[:R * 32].view(R, 32), z(R, 2 * Fb), buf[(R - 1) * 32 + Fb:(R - 1) * 32 + Fb + kd].view(R, Kp), Fb)
+        _err(native.stft_magnitude_bwd, buf[:R * 32].view(R, 32), z(R, 2 * Fb),
+             buf[(R - 1) * 32 + Fb - 1:(R - 1) * 32 + Fb - 1 + kd].view(R, Kp), Fb, match="must not be one of the inputs")
+        buf, k, kt = z(3 * B * n_mel * n), B * n_mel * n, B * n_mel * 2
+        out, tgt = buf[:k].view(B, n_mel, n), buf[2 * k:2 * k + kt].view(B, n_mel, 2)
+        native.mel_l1_bwd(out, tgt, None, z(1), 8, buf[k:2 * k].view(B, n_mel, n))
+        _err(native.mel_l1_bwd, out, tgt, None, z(1), 8, buf[k - 1:2 * k - 1].view(B, n_mel, n), match="must not be one of the inputs")
+        _err(native.mel_l1_bwd, out, tgt, None, z(1), 8, buf[k + 1:2 * k + 1].view(B, n_mel, n), match="must not be one of the inputs")
     finally:
         native.set_validate_only(False)
 

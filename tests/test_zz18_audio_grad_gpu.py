@@ -24,11 +24,15 @@ The largest ratio of an fp32 figure to the float32 autograd's is 1.20 (the half-
 float64 by 1.7e-9 to 1.7e-8 relative (the float32 autograd's by 1.7e-9 to 1.2e-7).
 """
 import functools
+import json
+import os
+import sys
 
 import pytest
 import torch
 
 import audio_grad_ref as ar
+import golden_util as gu
 import vocos_grad_ref as gr
 import vocos_ref as vr
 
@@ -333,3 +337,30 @@ def test_vocos_fine_tuning_loop(native_lib):
             bad.append((n, e, lim))
     print("FIGURE vocos step 0 worst ratio to the limit %.3f (loss gradient at the audio: float32 autograd %.3e)" % (worst, e_loss))
     assert not bad, bad
+
+
+# ---- the shared front end, backward tail and device helpers move no bit -------------------------------------------------------
+def _digests(section):
+    sys.path.insert(0, gu.GOLDEN_DIR)
+    try:
+        import make_golden_audio_digests as mk
+    finally:
+        sys.path.remove(gu.GOLDEN_DIR)
+    with open(os.path.join(gu.GOLDEN_DIR, "audio_digests.json")) as fh:
+        return mk, json.load(fh)[section]
+
+
+def test_bits_equal_the_digests_from_before_the_shared_helpers(native_lib):
+    """tests/golden/audio_digests.json was written by the commit before audio.py's STFT front ends and spectral backward tails
+    became one each and the row kernels took their helpers from csrc/common.h: mel_spectrogram (A, C) and its gradient, MelLoss
+    (C, full and ragged), STFT.transform, griffin_lim (2 iterations, ragged) per precision, stft_magnitude_bwd alone with a
+    zero tail longer than F; and the two clients of the shared wave sum that no other fixture pins (Vocos' LayerNorm backward,
+    WaveGlow's weight-norm fold)."""
+    mk, want = _digests("mel")
+    got = mk.digests_mel()
+    assert set(got) == set(want) and len(want) == 14
+    assert got == want, sorted(k for k in want if got[k] != want[k])
+    mk, want = _digests("wave_sum_clients")
+    got = mk.digests_wave_sum_clients()
+    assert set(got) == set(want) and len(want) == 6
+    assert got == want, sorted(k for k in want if got[k] != want[k])

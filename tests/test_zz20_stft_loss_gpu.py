@@ -22,11 +22,15 @@ float64 by 8e-9 to 8e-8 relative, exactly the float32 autograd's figures; the te
 2.6e-7).
 """
 import functools
+import json
+import os
+import sys
 
 import pytest
 import torch
 
 import audio_grad_ref as ar
+import golden_util as gu
 import stft_loss_ref as sr
 import vocos_ref as vr
 
@@ -307,3 +311,20 @@ def test_a_second_step_allocates_what_the_first_did(native_lib):
     _, allocs = _steps(4, 1.0, warmup=1)
     print("\nFIGURE driver steps: device allocations per step after the warm-up %s" % (allocs,))
     assert allocs[0] > 0 and allocs[1] == allocs[0] and allocs[2] == allocs[0] and allocs[3] == allocs[0], allocs
+
+
+# ---- the shared front end, backward tail and device helpers move no bit -------------------------------------------------------
+def test_bits_equal_the_digests_from_before_the_shared_helpers(native_lib):
+    """tests/golden/audio_digests.json was written by the commit before the loss took its STFT front end and its spectral
+    backward tail from ``audio.STFT`` and its device helpers from csrc/common.h: value, ``last_terms`` and gradient for the cases
+    A and Cr at R = 3 and R = 1 per precision, and stft_loss_bwd alone with a zero tail longer than F."""
+    sys.path.insert(0, gu.GOLDEN_DIR)
+    try:
+        import make_golden_audio_digests as mk
+    finally:
+        sys.path.remove(gu.GOLDEN_DIR)
+    with open(os.path.join(gu.GOLDEN_DIR, "audio_digests.json")) as fh:
+        want = json.load(fh)["stft_loss"]
+    got = mk.digests_stft_loss()
+    assert set(got) == set(want) and len(want) == 9
+    assert got == want, sorted(k for k in want if got[k] != want[k])
