@@ -961,6 +961,24 @@ int t2amd_stft_loss_bwd_f32(const float* spec_x, long long ldx, const float* spe
 int t2amd_stft_loss_sum_f32(const float* parts, long long stride, long long part_floats, int R, long long total, float* out,
                             void* stream);
 
+/* Sample-rate conversion (csrc/resample.hip).  o = orig / gcd, n = new / gcd; x (B, ldx) rows of T samples, y (B, ldy) rows of
+ * Tout = ceil(n T / o); lengths[b]: the samples of utterance b (device int32, clamped to [0, T]; NULL: all T).  No atomics. */
+/* The tile of a launch with P phases of S taps, input period I and first-tap + S <= Kd: *npw = outputs per workgroup, *tab_lds =
+ * 1 when the phase table is staged in LDS, 0 when it is read from memory.  An error when the table holds more than 2^24 taps or
+ * the input window of 256 outputs exceeds 4096 samples. */
+int t2amd_resample_plan(int P, int I, int S, int Kd, int* npw, int* tab_lds);
+/* y[b][q n + j] = sum_s tab[j][s] xpad[q o + first[j] + s], ascending s, xpad = x[b] with `width` zeros in front and zeros at and
+ * beyond lengths[b] whatever the buffer holds; tab (n, S), first (n) with first[j] + S <= 2 width + o.  All Tout columns are
+ * written, exact zeros at and beyond ceil(n lengths[b] / o). */
+int t2amd_resample_fwd_f32(const float* x, long long ldx, const int* lengths, int B, long long T, float* y, long long ldy,
+                           long long Tout, const float* tab, const int* first, int o, int n, int S, int width, void* stream);
+/* The adjoint as a gather: d_x[b][q o + r] = sum_s btab[r][s] d_ypad[q n + bfirst[r] + s], ascending s (ascending output index),
+ * d_ypad = d_y[b] with `wpad` zeros in front, not read at and beyond ceil(n lengths[b] / o); btab (o, Sb), bfirst (o) with
+ * bfirst[r] + Sb <= Kd.  All T columns are written, exact zeros at and beyond lengths[b]. */
+int t2amd_resample_bwd_f32(const float* d_y, long long ldy, const int* lengths, int B, long long T, long long Tout, float* d_x,
+                           long long ldx, const float* btab, const int* bfirst, int o, int n, int Sb, int wpad, int Kd,
+                           void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
  * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are

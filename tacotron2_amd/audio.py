@@ -50,6 +50,10 @@ sqrt gives NaN there).
 ``MultiResolutionSTFTLoss()(audio, target_audio, lengths)`` is the spectral-convergence plus log-magnitude loss over several STFT
 geometries (csrc/stft_loss.hip), again one autograd function from the samples to the scalar: fused row
 kernels straight off the two spectra, fixed-order float64 partial sums, no atomics and no host synchronisation.
+
+``Resample(orig_freq, new_freq)(x, lengths)`` / ``resample(x, orig_freq, new_freq, lengths)`` convert the sampling rate
+(csrc/resample.hip): band-limited sinc interpolation with a Hann window as a polyphase gather, its adjoint as
+a gather of the same shape, one autograd function, ragged batches equal to their utterances alone bit for bit.
 """
 import os
 
@@ -767,11 +771,177 @@ class _MultiResolutionSTFTLoss(torch.autograd.Function):
         return None, d_y.to(ctx.y_device), None, None, None
 
 
-def precompute_mels(filelist, hparams, out_dir, out_filelist=None):
+def resample_geometry(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """-> (o, n, base, width) of DESIGN.md section 15: o = orig / gcd, n = new / gcd, base = min(o, n) rolloff, width =
+    ceil(W o / base)."""
+    import math
+    orig_freq, new_freq, W = int(orig_freq), int(new_freq), int(lowpass_filter_width)
+    if orig_freq < 1 or new_freq < 1:
+        raise ValueError("resample: the rates must be positive, got %d -> %d" % (orig_freq, new_freq))
+    if W < 1 or not 0.0 < float(rolloff) <= 1.0:
+        raise ValueError("resample: lowpass_filter_width >= 1 and 0 < rolloff <= 1, got %r and %r" % (lowpass_filter_width, rolloff))
+    g = math.gcd(orig_freq, new_freq)
+    o, n = orig_freq // g, new_freq // g
+    base = min(o, n) * float(rolloff)
+    return o, n, base, int(math.ceil(W * o / base))
+
+
+def resample_tables(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """The host tables of ``Resample`` (numpy), DESIGN.md section 15.  ``dense`` (n, 2 width + o) float32 is the definition:
+    h[j][k] = sinc(t) cos^2(pi t / (2 W)) base / o with t = ((k - width) / o - j / n) base where |t| < W and exactly 0 elsewhere,
+    computed in float64 and rounded once.  ``tab`` (n, S) and ``first`` (n) are its compact form: tab[j][s] = dense[j][first[j] +
+    s], every tap with |t| < W inside.  ``btab`` (o, Sb), ``bfirst`` (o), ``wpad``, ``Kd`` are the same float32 coefficients
+    regrouped for the adjoint: d_x[q o + r] = sum_s btab[r][s] d_y[q n + bfirst[r] + s - wpad], ascending output index."""
+    o, n, base, width = resample_geometry(orig_freq, new_freq, lowpass_filter_width, rolloff)
+    W = int(lowpass_filter_width)
+    K = 2 * width + o
+    k = np.arange(K, dtype=np.float64)
+    j = np.arange(n, dtype=np.float64)
+    t = ((k[None, :] - width) / o - j[:, None] / n) * base
+    inside = np.abs(t) < W
+    pt = np.pi * t
+    sinc = np.where(t == 0.0, 1.0, np.sin(pt) / np.where(t == 0.0, 1.0, pt))
+    dense = np.where(inside, sinc * np.cos(pt / (2.0 * W)) ** 2 * (base / o), 0.0).astype(np.float32)
+
+    def compact(values, mask):
+        """Rows of `values` cut to the columns [first, first + S) that hold every True of `mask`."""
+        cols = mask.shape[1]
+        lo = mask.argmax(axis=1)
+        hi = cols - mask[:, ::-1].argmax(axis=1)
+        S = int((hi - lo).max())
+        first = np.minimum(lo, cols - S).astype(np.int32)
+        return np.ascontiguousarray(values[np.arange(mask.shape[0])[:, None], first[:, None] + np.arange(S)[None, :]]), first
+
+    tab, first = compact(dense, inside)
+    # the adjoint: input i = Q o + r is read by output m = (Q + c) n + j through tap k = r + width - c o
+    cmin, cmax = -((width + o - 1) // o), (o - 1 + width) // o
+    D = (cmax - cmin + 1) * n
+    bdense = np.zeros((o, D), dtype=np.float32)
+    bmask = np.zeros((o, D), dtype=bool)
+    r = np.arange(o)
+    for c in range(cmin, cmax + 1):
+        kk = r + width - c * o
+        ok = (kk >= 0) & (kk < K)
+        cols = slice((c - cmin) * n, (c - cmin + 1) * n)
+        bdense[ok, cols] = dense[:, kk[ok]].T
+        bmask[ok, cols] = inside[:, kk[ok]].T
+    btab, bfirst = compact(bdense, bmask)
+    shift = int(bfirst.min())
+    bfirst = (bfirst - shift).astype(np.int32)
+    return {"o": o, "n": n, "width": width, "dense": dense, "tab": tab, "first": first, "btab": btab, "bfirst": bfirst,
+            "wpad": -cmin * n - shift, "Kd": int(bfirst.max()) + btab.shape[1]}
+
+
+class Resample(torch.nn.Module):
+    """Sample-rate conversion on the GPU (csrc/resample.hip): band-limited sinc interpolation with a Hann
+    window, ``resample_tables``' definition.  ``forward(x, lengths=None)`` takes (T,), (B, T) or (B, 1, T) float32 device samples
+    and returns the same rank with ``output_length(T)`` = ceil(new T / orig) samples; with ``lengths`` (samples per utterance) the
+    samples at and beyond them read as zero, the result is 0 beyond the new lengths, and (y, new lengths) is returned.  One
+    autograd function, two launches in all; the only kept state is the lengths.  ``orig_freq == new_freq`` returns its input
+    unchanged.  There is no CPU path."""
+
+    def __init__(self, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+        super().__init__()
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self.lowpass_filter_width, self.rolloff = int(lowpass_filter_width), float(rolloff)
+        self.o, self.n, _, self.width = resample_geometry(orig_freq, new_freq, lowpass_filter_width, rolloff)
+        self._host = None
+        self._lazy = {}                 # per device: the four tables (plain attributes, not buffers)
+
+    def host_tables(self):
+        if self._host is None:
+            self._host = resample_tables(self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff)
+        return self._host
+
+    def tables(self, device):
+        """Device tables, built on first use: ``tab`` (n, S), ``first`` (n), ``btab`` (o, Sb), ``bfirst`` (o), with the host
+        integers ``wpad`` and ``Kd`` of the adjoint."""
+        def build(device):
+            h = self.host_tables()
+            out = dict((k, torch.from_numpy(h[k]).to(device)) for k in ("tab", "first", "btab", "bfirst"))
+            out["wpad"], out["Kd"] = h["wpad"], h["Kd"]
+            return out
+        return _per_device(self._lazy, 'resample', device, build)
+
+    def table_paths(self):
+        """(forward, backward): 'lds' where the launch stages its phase table in LDS, 'memory' where it reads it from memory."""
+        h = self.host_tables()
+        fwd = nv.resample_plan(self.n, self.o, h["tab"].shape[1], 2 * self.width + self.o)[1]
+        bwd = nv.resample_plan(self.o, self.n, h["btab"].shape[1], h["Kd"])[1]
+        return tuple('lds' if p else 'memory' for p in (fwd, bwd))
+
+    def output_length(self, T):
+        """ceil(new T / orig) for an int or each element of a sequence."""
+        if isinstance(T, (list, tuple)):
+            return [self.output_length(v) for v in T]
+        return -(-self.n * int(T) // self.o)
+
+    def forward(self, x, lengths=None):
+        if not torch.is_tensor(x) or x.dtype != torch.float32:
+            raise TypeError("Resample: expected a float32 tensor, got %s" % (x.dtype if torch.is_tensor(x) else type(x).__name__))
+        if x.dim() not in (1, 2, 3) or (x.dim() == 3 and x.shape[1] != 1) or x.shape[-1] < 1 or x.shape[0] < 1:
+            raise ValueError("Resample: expected (T,), (B, T) or (B, 1, T) samples, got shape %s" % (tuple(x.shape),))
+        _require_device(x)
+        rows = x.reshape(-1, x.shape[-1])
+        lens = _lengths(lengths, rows.shape[0], rows.shape[1], "Resample: ")
+        if self.o == self.n:
+            return x if lens is None else (x, list(lens))
+        y = _Resample.apply(self, rows, lens)
+        y = y.reshape(tuple(x.shape[:-1]) + (y.shape[-1],))
+        return y if lens is None else (y, self.output_length(list(lens)))
+
+
+class _Resample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mod, x, lens):
+        xs = x.detach()
+        if xs.stride(1) != 1:
+            xs = xs.contiguous()
+        tb = mod.tables(xs.device)
+        B, T = xs.shape
+        lens_dev = None if lens is None else torch.tensor(lens, dtype=torch.int32).to(xs.device)
+        y = torch.empty(B, mod.output_length(T), dtype=torch.float32, device=xs.device)
+        nv.resample_fwd(xs, lens_dev, y, tb["tab"], tb["first"], mod.o, mod.n, mod.width)
+        ctx.mod, ctx.kept, ctx.x_shape = mod, (lens_dev,), (B, T)
+        return y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        (lens_dev,) = _take_kept(ctx, "Resample")
+        mod, (B, T) = ctx.mod, ctx.x_shape
+        d_y = d_y.to(dtype=torch.float32)
+        if d_y.stride(1) != 1:
+            d_y = d_y.contiguous()
+        tb = mod.tables(d_y.device)
+        d_x = torch.empty(B, T, dtype=torch.float32, device=d_y.device)
+        nv.resample_bwd(d_y, lens_dev, d_x, tb["btab"], tb["bfirst"], mod.o, mod.n, tb["wpad"], tb["Kd"])
+        return None, d_x, None
+
+
+_RESAMPLERS = {}
+
+
+def resample(x, orig_freq, new_freq, lengths=None):
+    """``Resample(orig_freq, new_freq)(x, lengths)`` with the modules (and so their tables) of the last few rate pairs cached."""
+    key = (int(orig_freq), int(new_freq))
+    mod = _RESAMPLERS.pop(key, None)
+    if mod is None:
+        mod = Resample(*key)
+        while len(_RESAMPLERS) >= 8:
+            _RESAMPLERS.pop(next(iter(_RESAMPLERS)))
+    _RESAMPLERS[key] = mod              # most recently used last
+    return mod(x, lengths)
+
+
+_resample = resample                    # for the callers below whose flag is named ``resample``
+
+
+def precompute_mels(filelist, hparams, out_dir, out_filelist=None, resample=False):
     """Run every wav of a ``path|text`` filelist through the GPU front end once and write
     ``<out_dir>/<stem>.npy`` (n_mel, frames) float32 — the files the reference's
     ``load_mel_from_disk=True`` path reads (hparams.py:27, data_utils.py:50-55).  Optionally writes
-    the matching filelist.  Returns the number of utterances."""
+    the matching filelist.  Returns the number of utterances.  ``resample=True`` converts a file at another
+    rate to ``hparams.sampling_rate`` on the GPU (``Resample``) instead of refusing it."""
     from .utils import load_filepaths_and_text, load_wav_to_torch
     stft = TacotronSTFT(hparams.filter_length, hparams.hop_length, hparams.win_length, hparams.n_mel_channels,
                         hparams.sampling_rate, hparams.mel_fmin, hparams.mel_fmax)
@@ -780,9 +950,12 @@ def precompute_mels(filelist, hparams, out_dir, out_filelist=None):
     lines = []
     for fields in rows:
         audio, sr = load_wav_to_torch(fields[0])
+        audio = (audio / hparams.max_wav_value).unsqueeze(0)
         if sr != hparams.sampling_rate:
-            raise ValueError("%s: sampling rate %d, expected %d" % (fields[0], sr, hparams.sampling_rate))
-        mel = stft.mel_spectrogram((audio / hparams.max_wav_value).unsqueeze(0)).squeeze(0)
+            if not resample:
+                raise ValueError("%s: sampling rate %d, expected %d" % (fields[0], sr, hparams.sampling_rate))
+            audio = _resample(audio.to(stft.mel_basis.device), sr, hparams.sampling_rate).clamp_(-1.0, 1.0)
+        mel = stft.mel_spectrogram(audio).squeeze(0)
         dst = os.path.join(out_dir, os.path.splitext(os.path.basename(fields[0]))[0] + '.npy')
         np.save(dst, mel.cpu().numpy())
         lines.append('|'.join([dst] + fields[1:]))

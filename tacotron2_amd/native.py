@@ -289,6 +289,7 @@ SYMBOLS = [
     "t2amd_mel_l1_fwd_f32", "t2amd_mel_l1_bwd_f32",
     "t2amd_stft_loss_rows_per_slot", "t2amd_stft_loss_fwd_f32", "t2amd_stft_loss_finish_f64", "t2amd_stft_loss_bwd_f32",
     "t2amd_stft_loss_sum_f32",
+    "t2amd_resample_plan", "t2amd_resample_fwd_f32", "t2amd_resample_bwd_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
@@ -404,6 +405,9 @@ def _argtypes():
         "t2amd_stft_loss_finish_f64": [_P, _L, _P, _P, _I, _F, _F, _P, _P, _P, _P],
         "t2amd_stft_loss_bwd_f32": [_P, _L, _P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _P, _L, _L, _P],
         "t2amd_stft_loss_sum_f32": [_P, _L, _L, _I, _L, _P, _P],
+        "t2amd_resample_plan": [_I, _I, _I, _I, pt(C.c_int), pt(C.c_int)],
+        "t2amd_resample_fwd_f32": [_P, _L, _P, _I, _L, _P, _L, _L, _P, _P, _I, _I, _I, _I, _P],
+        "t2amd_resample_bwd_f32": [_P, _L, _P, _I, _L, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _P],
         "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
         "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
@@ -1784,6 +1788,45 @@ def stft_loss_sum(parts, out):
         raise NativeError("stft_loss_sum: parts %s beside out %s" % (tuple(parts.shape), tuple(out.shape)))
     _check(load().t2amd_stft_loss_sum_f32(ptr(_fullc(parts)), _i64(out.numel()), _i64(parts.numel()), int(R), _i64(out.numel()),
                                           ptr(_fullc(out)), _stream()), "t2amd_stft_loss_sum_f32")
+
+
+# ---- sample-rate conversion (csrc/resample.hip) -----------------------------------------------------------------------------
+def resample_plan(P, I, S, Kd):
+    """-> (outputs per workgroup, True when the phase table is staged in LDS) of a resample launch with P phases of S taps, input
+    period I and first-tap + S <= Kd; NativeError where the library refuses the geometry."""
+    npw, lds = C.c_int(0), C.c_int(0)
+    _check(load().t2amd_resample_plan(int(P), int(I), int(S), int(Kd), C.byref(npw), C.byref(lds)), "t2amd_resample_plan")
+    return npw.value, bool(lds.value)
+
+
+def _resample_args(who, x, y, lengths, tab, first, phases):
+    px, ldx, B, T = _mat(x)
+    py, ldy, By, Tout = _mat(y)
+    if By != B or tab.dim() != 2 or tab.shape[0] != phases or first.numel() != phases or first.dtype != torch.int32:
+        raise NativeError("%s: shape mismatch x=%s y=%s table=%s first=%s for %d phases"
+                          % (who, tuple(x.shape), tuple(y.shape), tuple(tab.shape), tuple(first.shape), phases))
+    if lengths is not None and (lengths.dtype != torch.int32 or lengths.dim() != 1 or lengths.numel() != B
+                                or not lengths.is_contiguous()):
+        raise NativeError("%s: lengths must be a contiguous int32 vector of %d sample counts" % (who, B))
+    return px, ldx, py, ldy, B, T, Tout
+
+
+def resample_fwd(x, lengths, y, tab, first, o, n, width):
+    """y (B, ceil(n T / o)) = the polyphase gather of x (B, T) with the compact table ``tab`` (n, S) and first-tap indices
+    ``first`` (n, int32); x reads as zero at and beyond ``lengths`` (device int32 or None), y is 0 beyond the new lengths."""
+    px, ldx, py, ldy, B, T, Tout = _resample_args("resample_fwd", x, y, lengths, tab, first, int(n))
+    _check(load().t2amd_resample_fwd_f32(px, _i64(ldx), None if lengths is None else ptr(lengths, torch.int32), B, _i64(T), py,
+                                         _i64(ldy), _i64(Tout), ptr(_fullc(tab)), ptr(_fullc(first), torch.int32), int(o), int(n),
+                                         int(tab.shape[1]), int(width), _stream()), "t2amd_resample_fwd_f32")
+
+
+def resample_bwd(d_y, lengths, d_x, btab, bfirst, o, n, wpad, Kd):
+    """d_x (B, T) = the adjoint of ``resample_fwd`` applied to d_y (B, ceil(n T / o)) as a gather with the regrouped table ``btab``
+    (o, Sb) and ``bfirst`` (o, int32); d_y is not read beyond the new lengths, d_x is 0 at and beyond ``lengths``."""
+    px, ldx, py, ldy, B, T, Tout = _resample_args("resample_bwd", d_x, d_y, lengths, btab, bfirst, int(o))
+    _check(load().t2amd_resample_bwd_f32(py, _i64(ldy), None if lengths is None else ptr(lengths, torch.int32), B, _i64(T),
+                                         _i64(Tout), px, _i64(ldx), ptr(_fullc(btab)), ptr(_fullc(bfirst), torch.int32), int(o),
+                                         int(n), int(btab.shape[1]), int(wpad), int(Kd), _stream()), "t2amd_resample_bwd_f32")
 
 
 # ----------------------------------------------------------------------------

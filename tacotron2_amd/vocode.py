@@ -9,7 +9,8 @@
 Reads (n_mel, n) float32 log-mels (what ``precompute_mels`` writes) or (B, n_mel, n) batches (one wav per item,
 ``<stem>_<b>.wav``), vocodes them as one ragged batch (``TacotronSTFT.vocode``, or ``WaveGlow.infer`` and optionally
 ``Denoiser`` with ``--waveglow``, or ``hifigan.Generator.infer`` with ``--hifigan``, or ``vocos.Vocos.infer`` with ``--vocos``: 256 samples per mel frame) and writes ``DIR/<stem>.wav``: 16-bit PCM at
-``hparams.sampling_rate``, the signal clipped to [-1, 1] and scaled by ``max_wav_value``.
+``hparams.sampling_rate``, the signal clipped to [-1, 1] and scaled by ``max_wav_value``.  ``--sampling-rate R`` converts the
+vocoder's output to R Hz first (``audio.Resample``) and the header says R.
 """
 import argparse
 import os
@@ -37,6 +38,8 @@ def main(argv=None):
     ap.add_argument("--denoise", type=float, default=0.0, metavar="STRENGTH",
                     help="WaveGlow Denoiser strength (default 0 = off)")
     ap.add_argument("--hparams", default="", help="comma-separated name=value overrides")
+    ap.add_argument("--sampling-rate", type=int, default=None, metavar="R",
+                    help="convert the vocoder's output to R Hz on the GPU before the clip (default: hparams.sampling_rate)")
     args = ap.parse_args(argv)
     if args.hifigan:
         # the generator draws no noise, and Denoiser is built from a WaveGlow's bias response
@@ -112,6 +115,16 @@ def main(argv=None):
             np.random.seed(args.seed)
         wav = stft.vocode(torch.from_numpy(batch), lengths=lengths, n_iters=args.iters, precision=args.precision).cpu().numpy()
         n_samples = [(n - 1) * hp.hop_length for n in lengths]
+    rate = hp.sampling_rate
+    if args.sampling_rate is not None and args.sampling_rate != rate:
+        if args.sampling_rate < 1:
+            ap.error("--sampling-rate must be positive")
+        if min(n_samples) < 1:
+            raise SystemExit("--sampling-rate: an utterance of %d samples cannot be converted" % min(n_samples))
+        from .audio import resample
+        sig = torch.from_numpy(np.ascontiguousarray(wav[:, :max(n_samples)], dtype=np.float32)).cuda()
+        sig, n_samples = resample(sig, rate, args.sampling_rate, lengths=n_samples)
+        wav, rate = sig.cpu().numpy(), args.sampling_rate
     from scipy.io.wavfile import write
     os.makedirs(args.out_dir, exist_ok=True)
     for b, name in enumerate(names):
@@ -119,7 +132,7 @@ def main(argv=None):
         # [-1, 1] * max_wav_value, kept inside int16 (1.0 * 32768 would wrap)
         pcm = np.clip(np.clip(wav[b, :T], -1.0, 1.0) * hp.max_wav_value, -32768, 32767).astype(np.int16)
         dst = os.path.join(args.out_dir, name + ".wav")
-        write(dst, hp.sampling_rate, pcm)
+        write(dst, rate, pcm)
         print(dst, T, "samples")
     return 0
 
