@@ -449,7 +449,9 @@ def test_batched_encoder_bilstm_bptt_persistent_matches_the_launch_chain(native_
     gradient as a split-bf16 (hi + lo) MFMA product against W_hh^T rows in registers -- against the chain of 2 T launches
     (pointwise cell backward + exact-f32 recurrent product) on the same ragged batch.  Tolerance: the split product carries
     ~2^-17 per term over K = 4H = 1024 and the error travels T steps back: max |diff| < 2e-5 of the slab's largest gradient
-    (measured ~1e-6); rows behind an utterance's length are exactly zero in both; partial row groups (B = 7, 40) included."""
+    (measured against a float64 restatement of the operation, tests/test_zz7b_encoder_bilstm_ref_gpu.py: at most 1.5e-6 of it
+    over H = 64 .. 256, T <= 23; the chain itself lies within 2.2e-7); rows behind an utterance's length are exactly zero in
+    both; partial row groups (B = 7, 40) included."""
     from tacotron2_amd import native as nv
     E = 2 * H
     g = torch.Generator().manual_seed(B * 977 + T)
@@ -506,7 +508,8 @@ def test_batched_encoder_bilstm_bptt_persistent_matches_the_launch_chain(native_
         scale = float(c.abs().max())
         assert float((c - p).abs().max()) < 2e-5 * scale, (d, float((c - p).abs().max()), scale)
         for b in range(B):
-            assert float(p[b, int(lens_c[b]):].abs().max()) == 0.0 if int(lens_c[b]) < T else True
+            if int(lens_c[b]) < T:
+                assert float(p[b, int(lens_c[b]):].abs().max()) == 0.0
 
 
 @pytest.mark.parametrize("B", [6, 12])
