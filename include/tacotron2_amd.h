@@ -979,6 +979,24 @@ int t2amd_resample_bwd_f32(const float* d_y, long long ldy, const int* lengths, 
                            long long ldx, const float* btab, const int* bfirst, int o, int n, int Sb, int wpad, int Kd,
                            void* stream);
 
+/* Mel-cepstral distortion under dynamic time warping (csrc/dtw.hip).  No atomics, one writer per element. */
+/* Rows of a band of the DTW wavefront = lanes of its workgroup. */
+int t2amd_dtw_width(void);
+/* out (B, T, K) contiguous: out[b][t][k] = sum_m basis[k][m] mel[b * ldb + m * ldm + t], ascending m; basis (K, n_mel) contiguous,
+ * 1 <= K <= 32, K n_mel <= 8192.  Rows at and beyond lengths[b] (device int32, clamped to [0, T]; NULL: all T) are zeros. */
+int t2amd_mel_cepstrum_f32(const float* mel, long long ldb, long long ldm, const int* lengths, int B, int n_mel, int T,
+                           const float* basis, int K, float* out, void* stream);
+/* Pair p: a + p sa holds n_a rows of K floats, b + p sb holds n_b rows; n_a = na[p], n_b = nb[p] (device int32, NULL: Ta, Tb),
+ * 1 to 4096 each.  d(i,j) = sqrt(sum_k (a_ik - b_jk)^2); D(i,j) = d(i,j) + min(D(i-1,j-1), D(i-1,j), D(i,j-1)), D(0,0) = d(0,0);
+ * among equal predecessors the diagonal, then (i-1,j), then (i,j-1).  cost[p] = D(n_a-1, n_b-1), steps[p] = the cells of that
+ * path.  path (NULL: not wanted): per pair a slab of path_rows x path_cols bytes, byte [i path_cols + j] = the predecessor chosen
+ * at (i,j): 0, 1 or 2 in the order above; bytes outside the pair's own n_a x n_b cells are not written. */
+int t2amd_dtw_f32(const float* a, long long sa, const float* b, long long sb, const int* na, const int* nb, int B, int Ta, int Tb,
+                  int K, float* cost, int* steps, unsigned char* path, int path_rows, int path_cols, void* stream);
+/* out (B, L, 2) int32: the path of pair p as (i, j) from (0,0) to (n_a-1, n_b-1), steps[p] entries, then -1.  One lane per pair. */
+int t2amd_dtw_backtrack(const unsigned char* path, int path_rows, int path_cols, const int* na, const int* nb, const int* steps,
+                        int B, int Ta, int Tb, int* out, int L, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
  * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are

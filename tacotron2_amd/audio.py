@@ -54,6 +54,10 @@ kernels straight off the two spectra, fixed-order float64 partial sums, no atomi
 ``Resample(orig_freq, new_freq)(x, lengths)`` / ``resample(x, orig_freq, new_freq, lengths)`` convert the sampling rate
 (csrc/resample.hip): band-limited sinc interpolation with a Hann window as a polyphase gather, its adjoint as
 a gather of the same shape, one autograd function, ragged batches equal to their utterances alone bit for bit.
+
+``MelCepstralDistortion()(mel_a, mel_b, len_a, len_b)`` scores two log-mels of different lengths (csrc/dtw.hip, DESIGN.md section
+16): ``mel_cepstrum`` (orthonormal DCT-II without c0), ``dtw`` (one workgroup per pair, fixed tie rule, path length carried with
+the cost, the path itself on request), MCD in dB per pair.  Evaluation only: no gradients.
 """
 import os
 
@@ -934,6 +938,123 @@ def resample(x, orig_freq, new_freq, lengths=None):
 
 
 _resample = resample                    # for the callers below whose flag is named ``resample``
+
+
+DTW_MAX_FRAMES = 4096
+DTW_MAX_COEF = 32
+MCD_DB = 10.0 / np.log(10.0) * np.sqrt(2.0)
+
+
+def cepstral_basis(n_mel, n_coef=13):
+    """(n_coef, n_mel) float32: row k-1 is sqrt(2 / N) cos(pi k (m + 1/2) / N), k = 1 ... n_coef, the orthonormal DCT-II without
+    c0, computed in float64 and rounded once."""
+    n_mel, n_coef = int(n_mel), int(n_coef)
+    if not 1 <= n_coef <= DTW_MAX_COEF:
+        raise ValueError("n_coef must lie in [1, %d], got %d" % (DTW_MAX_COEF, n_coef))
+    if n_mel < 1:
+        raise ValueError("n_mel must be positive, got %d" % n_mel)
+    k = np.arange(1, n_coef + 1, dtype=np.float64)[:, None]
+    m = np.arange(n_mel, dtype=np.float64)[None, :]
+    return (np.sqrt(2.0 / n_mel) * np.cos(np.pi * k * (m + 0.5) / n_mel)).astype(np.float32)
+
+
+_CEPSTRAL_BASES = {}
+
+
+def _frames(t, who, what):
+    """A float32 rank-3 device tensor, or an error in the words of the neighbouring modules."""
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise TypeError("%s: expected a float32 tensor, got %s" % (who, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if t.dim() != 3 or min(t.shape) < 1:
+        raise ValueError("%s: expected %s, got shape %s" % (who, what, tuple(t.shape)))
+    _require_device(t)
+    return t.detach()
+
+
+def mel_cepstrum(mel, lengths=None, n_coef=13):
+    """(B, n_mel, T) natural-log mel (what ``TacotronSTFT.mel_spectrogram`` returns) -> (B, T, n_coef) float32 mel cepstra
+    c_k = sqrt(2 / N) sum_m x_m cos(pi k (m + 1/2) / N), k = 1 ... n_coef, summed in ascending m (csrc/dtw.hip).  Rows at and
+    beyond ``lengths`` are zeros.  No gradient; there is no CPU path."""
+    mel = _frames(mel, "mel_cepstrum", "(B, n_mel, T) log-mels")
+    B, N, T = mel.shape
+    key = (N, int(n_coef))
+    if key not in _CEPSTRAL_BASES:
+        _CEPSTRAL_BASES[key] = {"host": torch.from_numpy(cepstral_basis(N, n_coef))}
+    if N * key[1] > 8192:
+        raise ValueError("mel_cepstrum: n_coef x n_mel must not exceed 8192, got %d x %d" % (key[1], N))
+    basis = _per_device(_CEPSTRAL_BASES[key], 'basis', mel.device, lambda d: _CEPSTRAL_BASES[key]["host"].to(d))
+    lens = None if lengths is None else _lengths(lengths, B, T, "mel_cepstrum: ")
+    if mel.stride(2) != 1 and T > 1:
+        mel = mel.contiguous()
+    out = torch.empty(B, T, key[1], dtype=torch.float32, device=mel.device)
+    nv.mel_cepstrum(mel, None if lens is None else torch.tensor(lens, dtype=torch.int32).to(mel.device), basis, out)
+    return out
+
+
+def dtw(x, y, x_lengths=None, y_lengths=None, return_path=False):
+    """Dynamic time warping of x (B, Tx, K) against y (B, Ty, K), float32 on the device (csrc/dtw.hip):
+    Euclidean local cost, steps (1,1), (1,0), (0,1), ties taken in that order.  -> ``cost`` (B,) float32, the accumulated cost of
+    the optimal path, ``steps`` (B,) int32, its number of cells, and with ``return_path`` also ``path`` (B, max n_x + max n_y - 1,
+    2) int32: the cells (i, j) from (0, 0) to (n_x - 1, n_y - 1), -1 beyond ``steps``.  Lengths lie in [1, min(T, 4096)]."""
+    x = _frames(x, "dtw", "(B, T, K) frames")
+    y = _frames(y, "dtw", "(B, T, K) frames")
+    if x.device != y.device:
+        raise ValueError("dtw: the two sequences live on %s and %s" % (x.device, y.device))
+    if x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2]:
+        raise ValueError("dtw: expected (B, Tx, K) and (B, Ty, K), got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+    B, Tx, K = x.shape
+    Ty = y.shape[1]
+    if not 1 <= K <= DTW_MAX_COEF:
+        raise ValueError("dtw: K must lie in [1, %d], got %d" % (DTW_MAX_COEF, K))
+    lx = _lengths(x_lengths, B, min(Tx, DTW_MAX_FRAMES), "dtw: x_", full=Tx)
+    ly = _lengths(y_lengths, B, min(Ty, DTW_MAX_FRAMES), "dtw: y_", full=Ty)
+    dev = x.device
+    na, nb = (torch.tensor(v, dtype=torch.int32).to(dev) for v in (lx, ly))
+    cost = torch.empty(B, dtype=torch.float32, device=dev)
+    steps = torch.empty(B, dtype=torch.int32, device=dev)
+    x, y = x.contiguous(), y.contiguous()
+    if not return_path:
+        nv.dtw(x, y, na, nb, cost, steps)
+        return cost, steps
+    slab = torch.empty(B, max(lx), max(ly), dtype=torch.uint8, device=dev)
+    path = torch.empty(B, max(lx) + max(ly) - 1, 2, dtype=torch.int32, device=dev)
+    nv.dtw(x, y, na, nb, cost, steps, slab)
+    nv.dtw_backtrack(slab, na, nb, steps, Tx, Ty, path)
+    return cost, steps, path
+
+
+class MelCepstralDistortion(torch.nn.Module):
+    """Mel-cepstral distortion under dynamic time warping, in dB per pair.  ``forward(mel_a, mel_b,
+    len_a=None, len_b=None)`` takes two (B, n_mel, T) natural-log mels of any two lengths and returns (B,) float32:
+    (10 / ln 10) sqrt(2) cost / steps with ``cost`` and ``steps`` those of ``dtw`` over the ``mel_cepstrum`` of each side.
+    ``last`` holds the ``cost``, ``steps``, ``len_a`` and ``len_b`` of the latest call (and ``path`` when ``return_path``).  An
+    evaluation figure: it runs under ``no_grad`` and returns tensors without a ``grad_fn``.  There is no CPU path."""
+
+    def __init__(self, n_coef=13, return_path=False):
+        super().__init__()
+        if not 1 <= int(n_coef) <= DTW_MAX_COEF:
+            raise ValueError("n_coef must lie in [1, %d], got %d" % (DTW_MAX_COEF, int(n_coef)))
+        self.n_coef, self.return_path = int(n_coef), bool(return_path)
+        self.last = None
+
+    @torch.no_grad()
+    def forward(self, mel_a, mel_b, len_a=None, len_b=None):
+        mel_a = _frames(mel_a, "MelCepstralDistortion", "(B, n_mel, T) log-mels")
+        mel_b = _frames(mel_b, "MelCepstralDistortion", "(B, n_mel, T) log-mels")
+        if mel_a.shape[:2] != mel_b.shape[:2]:
+            raise ValueError("MelCepstralDistortion: expected two (B, n_mel, T) log-mels of one B and n_mel, got %s and %s"
+                             % (tuple(mel_a.shape), tuple(mel_b.shape)))
+        B = mel_a.shape[0]
+        la = _lengths(len_a, B, min(mel_a.shape[2], DTW_MAX_FRAMES), "MelCepstralDistortion: len_a: ", full=mel_a.shape[2])
+        lb = _lengths(len_b, B, min(mel_b.shape[2], DTW_MAX_FRAMES), "MelCepstralDistortion: len_b: ", full=mel_b.shape[2])
+        ca = mel_cepstrum(mel_a[:, :, :max(la)], la, self.n_coef)
+        cb = mel_cepstrum(mel_b[:, :, :max(lb)], lb, self.n_coef)
+        out = dtw(ca, cb, la, lb, return_path=self.return_path)
+        cost, steps = out[0], out[1]
+        self.last = {"cost": cost, "steps": steps, "len_a": la, "len_b": lb}
+        if self.return_path:
+            self.last["path"] = out[2]
+        return cost * (float(MCD_DB) / steps.to(torch.float32))
 
 
 def precompute_mels(filelist, hparams, out_dir, out_filelist=None, resample=False):

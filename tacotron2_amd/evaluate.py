@@ -1,0 +1,144 @@
+"""Mel-cepstral distortion under dynamic time warping (MCD-DTW) of synthesised mels against recordings, on the GPU
+(``audio.MelCepstralDistortion``, csrc/dtw.hip).
+
+    python -m tacotron2_amd.evaluate --mels DIR_A DIR_B [--n-coef 13] [--batch 16] [-o FILE]
+    python -m tacotron2_amd.evaluate --checkpoint CKPT --filelist FILE [--hparams name=value,...] [--batch 16] [-o FILE]
+
+Directory mode pairs the ``.npy`` natural-log mels (n_mel, frames) of the two directories by file name; names present on one side
+only are listed and skipped.  Checkpoint mode builds the model and the data set the way ``train.py`` does, decodes every batch
+free-running (``model.inference(text, input_lengths)``) and scores ``mel_outputs_postnet[:, :, :last_inference_lengths]`` against
+the data set's mels.  Both print one line per utterance (name, frames A, frames B, path steps, MCD dB) and a final JSON line:
+count, mean, standard deviation, median, mean length ratio (A over B) and, in checkpoint mode, the decodes that ran into
+``max_decoder_steps``.  ``-o`` writes the same JSON to a file."""
+import argparse
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import audio
+
+
+def pair_directories(dir_a, dir_b):
+    """-> (sorted names in both, sorted names only in A, sorted names only in B) of the ``.npy`` files."""
+    def names(d):
+        return set(f for f in os.listdir(d) if f.endswith('.npy'))
+    a, b = names(dir_a), names(dir_b)
+    return sorted(a & b), sorted(a - b), sorted(b - a)
+
+
+def score_batch(mcd, mels_a, mels_b, device):
+    """Lists of (n_mel, frames) host mels -> [(frames A, frames B, steps, MCD dB)] of one ``MelCepstralDistortion`` call."""
+    def pad(mels):
+        n_mel, T = mels[0].shape[0], max(m.shape[1] for m in mels)
+        out = torch.zeros(len(mels), n_mel, T, dtype=torch.float32)
+        for i, m in enumerate(mels):
+            if m.dim() != 2 or m.shape[0] != n_mel or m.shape[1] < 1:
+                raise ValueError("expected (n_mel, frames) mels of one n_mel, got shape %s beside n_mel %d" % (tuple(m.shape), n_mel))
+            out[i, :, :m.shape[1]] = m
+        return out.to(device), [m.shape[1] for m in mels]
+    a, la = pad(mels_a)
+    b, lb = pad(mels_b)
+    db = mcd(a, b, la, lb).cpu().tolist()
+    steps = mcd.last["steps"].cpu().tolist()
+    return list(zip(la, lb, steps, db))
+
+
+def summarise(rows, extra=None):
+    """The JSON summary of [(name, frames A, frames B, steps, dB)]."""
+    db = np.array([r[4] for r in rows], dtype=np.float64)
+    ratio = np.array([r[1] / r[2] for r in rows], dtype=np.float64)
+    out = {"count": len(rows),
+           "mcd_db_mean": float(db.mean()) if len(rows) else None,
+           "mcd_db_std": float(db.std()) if len(rows) else None,
+           "mcd_db_median": float(np.median(db)) if len(rows) else None,
+           "length_ratio_mean": float(ratio.mean()) if len(rows) else None}
+    out.update(extra or {})
+    return out
+
+
+def _report(rows):
+    for name, fa, fb, steps, db in rows:
+        print("%s %d %d %d %.4f" % (name, fa, fb, steps, db))
+
+
+def evaluate_directories(dir_a, dir_b, n_coef=13, batch=16, device='cuda'):
+    both, only_a, only_b = pair_directories(dir_a, dir_b)
+    for side, names in (("A", only_a), ("B", only_b)):
+        for n in names:
+            print("unmatched (only in %s): %s" % (side, n))
+    mcd = audio.MelCepstralDistortion(n_coef)
+    rows = []
+    for k in range(0, len(both), batch):
+        names = both[k:k + batch]
+        ma = [torch.from_numpy(np.load(os.path.join(dir_a, n)).astype(np.float32)) for n in names]
+        mb = [torch.from_numpy(np.load(os.path.join(dir_b, n)).astype(np.float32)) for n in names]
+        got = [(n,) + r for n, r in zip(names, score_batch(mcd, ma, mb, device))]
+        _report(got)
+        rows += got
+    return rows, summarise(rows, {"unmatched": only_a + only_b})
+
+
+def evaluate_checkpoint(checkpoint, filelist, hparams, n_coef=13, batch=16):
+    from .data_utils import TextMelCollate, TextMelLoader
+    from .train import _read_checkpoint, load_model
+    model = load_model(hparams)
+    model.load_state_dict(_read_checkpoint(checkpoint)['state_dict'])
+    model.eval()
+    data = TextMelLoader(filelist, hparams)
+    collate = TextMelCollate(hparams.n_frames_per_step)
+    device = next(model.parameters()).device
+    mcd = audio.MelCepstralDistortion(n_coef)
+    rows, hit_max = [], 0
+    for k in range(0, len(data), batch):
+        idx = list(range(k, min(k + batch, len(data))))
+        items = [data[i] for i in idx]
+        # the collate sorts by text length, descending; the names follow it
+        order = torch.sort(torch.LongTensor([it[0].numel() for it in items]), dim=0, descending=True)[1].tolist()
+        text, input_lengths, mel, _, output_lengths = collate(items)
+        outs = model.inference(text.to(device).long(), input_lengths.to(device).long())
+        got_len = [int(v) for v in torch.as_tensor(model.last_inference_lengths).tolist()]
+        hit_max += sum(1 for v in got_len if v >= hparams.max_decoder_steps)
+        post = outs[1].float().cpu()
+        ma = [post[b, :, :max(1, got_len[b])] for b in range(len(idx))]
+        mb = [mel[b, :, :int(output_lengths[b])] for b in range(len(idx))]
+        names = [os.path.basename(data.audiopaths_and_text[idx[j]][0]) for j in order]
+        got = [(n,) + r for n, r in zip(names, score_batch(mcd, ma, mb, device))]
+        _report(got)
+        rows += got
+    return rows, summarise(rows, {"hit_max_decoder_steps": hit_max})
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--mels', nargs=2, metavar=('DIR_A', 'DIR_B'), help='two directories of .npy log-mels paired by file name')
+    ap.add_argument('--checkpoint', help='a Tacotron 2 checkpoint to decode free-running')
+    ap.add_argument('--filelist', help='the filelist (or synthetic:N) whose mels the decodes are scored against')
+    ap.add_argument('--hparams', type=str, help='comma separated name=value pairs')
+    ap.add_argument('--batch', type=int, default=16)
+    ap.add_argument('--n-coef', type=int, default=13, help='cepstral coefficients c1 ... cK, 1 to 32')
+    ap.add_argument('--device', default='cuda', help=argparse.SUPPRESS)
+    ap.add_argument('-o', '--output', help='write the JSON summary here as well')
+    args = ap.parse_args(argv)
+    if (args.mels is None) == (args.checkpoint is None):
+        ap.error("give either --mels DIR_A DIR_B or --checkpoint CKPT --filelist FILE")
+    if args.batch < 1:
+        ap.error("--batch must be positive")
+    if args.mels is not None:
+        _, summary = evaluate_directories(args.mels[0], args.mels[1], args.n_coef, args.batch, args.device)
+    else:
+        if not args.filelist:
+            ap.error("--checkpoint needs --filelist")
+        from .hparams import create_hparams
+        _, summary = evaluate_checkpoint(args.checkpoint, args.filelist, create_hparams(args.hparams), args.n_coef, args.batch)
+    line = json.dumps(summary)
+    print(line)
+    if args.output:
+        with open(args.output, 'w') as fh:
+            fh.write(line + "\n")
+    return summary
+
+
+if __name__ == '__main__':
+    main()

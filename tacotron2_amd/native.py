@@ -290,6 +290,7 @@ SYMBOLS = [
     "t2amd_stft_loss_rows_per_slot", "t2amd_stft_loss_fwd_f32", "t2amd_stft_loss_finish_f64", "t2amd_stft_loss_bwd_f32",
     "t2amd_stft_loss_sum_f32",
     "t2amd_resample_plan", "t2amd_resample_fwd_f32", "t2amd_resample_bwd_f32",
+    "t2amd_dtw_width", "t2amd_mel_cepstrum_f32", "t2amd_dtw_f32", "t2amd_dtw_backtrack",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
@@ -408,6 +409,10 @@ def _argtypes():
         "t2amd_resample_plan": [_I, _I, _I, _I, pt(C.c_int), pt(C.c_int)],
         "t2amd_resample_fwd_f32": [_P, _L, _P, _I, _L, _P, _L, _L, _P, _P, _I, _I, _I, _I, _P],
         "t2amd_resample_bwd_f32": [_P, _L, _P, _I, _L, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _P],
+        "t2amd_dtw_width": [],
+        "t2amd_mel_cepstrum_f32": [_P, _L, _L, _P, _I, _I, _I, _P, _I, _P, _P],
+        "t2amd_dtw_f32": [_P, _L, _P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P],
+        "t2amd_dtw_backtrack": [_P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P],
         "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
         "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
@@ -1827,6 +1832,66 @@ def resample_bwd(d_y, lengths, d_x, btab, bfirst, o, n, wpad, Kd):
     _check(load().t2amd_resample_bwd_f32(py, _i64(ldy), None if lengths is None else ptr(lengths, torch.int32), B, _i64(T),
                                          _i64(Tout), px, _i64(ldx), ptr(_fullc(btab)), ptr(_fullc(bfirst), torch.int32), int(o),
                                          int(n), int(btab.shape[1]), int(wpad), int(Kd), _stream()), "t2amd_resample_bwd_f32")
+
+
+# ---- mel-cepstral distortion under dynamic time warping (csrc/dtw.hip) ------------------------------------------------------------
+def dtw_width():
+    """Rows of a band of the DTW wavefront (the lanes of its workgroup)."""
+    return int(load().t2amd_dtw_width())
+
+
+def _pair_lengths(who, n, B):
+    if n is not None and (n.dtype != torch.int32 or n.dim() != 1 or n.numel() != B or not n.is_contiguous()):
+        raise NativeError("%s: lengths must be a contiguous int32 vector of %d frame counts" % (who, B))
+    return None if n is None else ptr(n, torch.int32)
+
+
+def mel_cepstrum(mel, lengths, basis, out):
+    """out (B, T, K) = the cepstra of the log-mel ``mel`` (B, n_mel, T) (unit stride along T) under ``basis`` (K, n_mel); rows at
+    and beyond ``lengths`` (device int32 or None) are zeros."""
+    if mel.dim() != 3 or basis.dim() != 2 or out.dim() != 3 or (mel.shape[2] > 1 and mel.stride(2) != 1) \
+            or basis.shape[1] != mel.shape[1] or tuple(out.shape) != (mel.shape[0], mel.shape[2], basis.shape[0]):
+        raise NativeError("mel_cepstrum: shape mismatch mel=%s stride %s basis=%s out=%s"
+                          % (tuple(mel.shape), mel.stride(), tuple(basis.shape), tuple(out.shape)))
+    B, N, T = mel.shape
+    ldm = mel.stride(1) if N > 1 else max(mel.stride(1), T)
+    ldb = mel.stride(0) if B > 1 else max(mel.stride(0), (N - 1) * ldm + T)
+    _check(load().t2amd_mel_cepstrum_f32(ptr(mel), _i64(ldb), _i64(ldm), _pair_lengths("mel_cepstrum", lengths, B), B, N, T,
+                                         ptr(_fullc(basis)), int(basis.shape[0]), ptr(_fullc(out)), _stream()),
+           "t2amd_mel_cepstrum_f32")
+
+
+def _dtw_slab(who, slab, B):
+    if slab.dtype != torch.uint8 or slab.dim() != 3 or slab.shape[0] != B or not slab.is_contiguous():
+        raise NativeError("%s: the predecessor slab must be a contiguous (B, rows, cols) uint8 tensor, got %s %s"
+                          % (who, slab.dtype, tuple(slab.shape)))
+    return ptr(slab, torch.uint8), int(slab.shape[1]), int(slab.shape[2])
+
+
+def dtw(a, b, na, nb, cost, steps, slab=None):
+    """cost (B,) float32 and steps (B,) int32 of the DTW of a (B, Ta, K) against b (B, Tb, K) (both contiguous) with ``na``, ``nb``
+    frames (device int32 or None); ``slab`` (B, rows, cols) uint8 receives the chosen predecessor of every cell when given."""
+    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[2] or cost.numel() != a.shape[0] \
+            or steps.numel() != a.shape[0]:
+        raise NativeError("dtw: shape mismatch a=%s b=%s cost=%s steps=%s"
+                          % (tuple(a.shape), tuple(b.shape), tuple(cost.shape), tuple(steps.shape)))
+    B, Ta, K = a.shape
+    Tb = b.shape[1]
+    ps, rows, cols = (None, 0, 0) if slab is None else _dtw_slab("dtw", slab, B)
+    _check(load().t2amd_dtw_f32(ptr(_fullc(a)), _i64(Ta * K), ptr(_fullc(b)), _i64(Tb * K), _pair_lengths("dtw", na, B),
+                                _pair_lengths("dtw", nb, B), B, Ta, Tb, K, ptr(_fullc(cost)), ptr(_fullc(steps), torch.int32), ps,
+                                rows, cols, _stream()), "t2amd_dtw_f32")
+
+
+def dtw_backtrack(slab, na, nb, steps, Ta, Tb, out):
+    """out (B, L, 2) int32 = the paths the predecessor bytes of ``dtw`` describe, forward, -1 beyond ``steps``."""
+    B = steps.numel()
+    ps, rows, cols = _dtw_slab("dtw_backtrack", slab, B)
+    if out.dim() != 3 or out.shape[0] != B or out.shape[2] != 2:
+        raise NativeError("dtw_backtrack: expected a (B, L, 2) path tensor, got %s" % (tuple(out.shape),))
+    _check(load().t2amd_dtw_backtrack(ps, rows, cols, _pair_lengths("dtw_backtrack", na, B), _pair_lengths("dtw_backtrack", nb, B),
+                                      ptr(_fullc(steps), torch.int32), B, int(Ta), int(Tb), ptr(_fullc(out), torch.int32),
+                                      int(out.shape[1]), _stream()), "t2amd_dtw_backtrack")
 
 
 # ----------------------------------------------------------------------------
