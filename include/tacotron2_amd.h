@@ -997,6 +997,21 @@ int t2amd_dtw_f32(const float* a, long long sa, const float* b, long long sb, co
 int t2amd_dtw_backtrack(const unsigned char* path, int path_rows, int path_cols, const int* na, const int* nb, const int* steps,
                         int B, int Ta, int Tb, int* out, int L, void* stream);
 
+/* F0 extraction by YIN (csrc/yin.hip).  No atomics, one writer per element. */
+/* The lag range of a geometry: *tau_min = floor(sr / fmax), *tau_max = ceil(sr / fmin).  An error where fmin >= fmax, the frame
+ * length L is odd or above 4096, hop < 1, tau_min < 2 or L / 2 + tau_max + 1 > L. */
+int t2amd_yin_plan(double sr, int L, int hop, double fmin, double fmax, int* tau_min, int* tau_max);
+/* x (B, ldx) rows of T samples; lengths[b]: the samples of utterance b (device int32, clamped to T; NULL: all T).  Utterance b has
+ * lengths[b] / hop + 1 frames; frame t is x[t hop - L/2 : t hop + L/2] with zeros outside the utterance.  Per frame:
+ * d(tau) = sum_{j < L/2} (f[j] - f[j+tau])^2, d'(tau) = d(tau) tau / (d(1) + .. + d(tau)) (1 where that sum is 0, d'(0) = 1); the lag
+ * is the smallest tau in [tau_min, tau_max] with d'(tau) < threshold, d'(tau) < d'(tau-1) and d'(tau) <= d'(tau+1) (voiced), else the
+ * first argmin of d' over the range (unvoiced); f0 = sr / (tau + shift) with the parabolic shift clipped to half a lag.
+ * f0, voiced (bytes 0 / 1), aperiodicity = d'(tau): (B, frames) contiguous, frames = T / hop + 1, zeros at and beyond an
+ * utterance's count.  dprime (NULL: not wanted): (B, frames, tau_max + 2) contiguous, d'(0 .. tau_max + 1), zeros likewise. */
+int t2amd_yin_f32(const float* x, long long ldx, const int* lengths, int B, long long T, int frames, int L, int hop, int tau_min,
+                  int tau_max, float sr, float threshold, float* f0, unsigned char* voiced, float* aperiodicity, float* dprime,
+                  void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
  * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are

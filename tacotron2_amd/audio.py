@@ -1057,6 +1057,87 @@ class MelCepstralDistortion(torch.nn.Module):
         return cost * (float(MCD_DB) / steps.to(torch.float32))
 
 
+def yin(y, lengths=None, sr=22050, frame_length=1024, hop_length=256, fmin=60.0, fmax=800.0, threshold=0.1, return_dprime=False):
+    """F0 by YIN (csrc/yin.hip) of y (B, T) or (T,), float32 on the device, unit stride along time.
+    Utterance b has ``lengths[b] // hop_length + 1`` frames, the mel front end's count; frame t is centred on sample t hop_length
+    and padded with zeros.  -> ``f0`` (B, frames) float32 in Hz (the best estimate on unvoiced frames too), ``voiced`` (B, frames)
+    bool, ``aperiodicity`` (B, frames) float32 = d'(tau); with ``return_dprime`` also the slab (B, frames, tau_max + 2) of
+    d'(0 .. tau_max + 1).  Frames at and beyond an utterance's count are 0 / False / 0.  Not differentiable: an estimator with a
+    discrete choice of lag; it detaches its input and returns tensors without a ``grad_fn``.  There is no CPU path."""
+    if not torch.is_tensor(y) or y.dtype != torch.float32:
+        raise TypeError("yin: expected a float32 tensor, got %s" % (y.dtype if torch.is_tensor(y) else type(y).__name__))
+    if y.dim() == 1:
+        y = y.unsqueeze(0)
+    if y.dim() != 2 or min(y.shape) < 1:
+        raise ValueError("yin: expected (B, T) or (T,) samples, got shape %s" % (tuple(y.shape),))
+    if y.shape[1] > 1 and y.stride(1) != 1:
+        raise ValueError("yin: the signal must have unit stride along time, got stride %s" % (y.stride(),))
+    _require_device(y)
+    y = y.detach()
+    B, T = y.shape
+    tau_min, tau_max = nv.yin_plan(sr, frame_length, hop_length, fmin, fmax)
+    lens = _lengths(lengths, B, T, "yin: ")
+    dev = y.device
+    frames = T // int(hop_length) + 1
+    f0 = torch.empty(B, frames, dtype=torch.float32, device=dev)
+    ap = torch.empty(B, frames, dtype=torch.float32, device=dev)
+    voiced = torch.empty(B, frames, dtype=torch.uint8, device=dev)
+    slab = torch.empty(B, frames, tau_max + 2, dtype=torch.float32, device=dev) if return_dprime else None
+    nv.yin(y, None if lens is None else torch.tensor(lens, dtype=torch.int32).to(dev), frame_length, hop_length, tau_min, tau_max,
+           sr, threshold, f0, voiced, ap, slab)
+    out = (f0, voiced.view(torch.bool), ap)
+    return out + (slab,) if return_dprime else out
+
+
+def f0_metrics(f0_a, voiced_a, f0_b, voiced_b, len_a=None, len_b=None, path=None, steps=None):
+    """The pitch figures of B pairs of F0 tracks (B, Ta) and (B, Tb), over the frames ``path`` pairs: the (B, L, 2) int32 path of
+    ``dtw`` / ``MelCepstralDistortion(return_path=True)`` with its ``steps`` (entries beyond ``steps`` or below 0 are left out).
+    Without a path, frame i is paired with frame i up to the shorter of ``len_a`` and ``len_b`` (None: all frames).  -> a dict of
+    (B,) tensors: ``f0_rmse_cents`` (root mean square of 1200 log2(fa / fb) over the steps where both are voiced), ``f0_corr``
+    (Pearson correlation over the same steps), ``vuv_error`` (share of steps whose flags differ), ``gross_pitch_error`` (share of
+    both-voiced steps with |fa / fb - 1| > 0.2), all float64, and ``voiced_steps`` (int64).  A pair with no both-voiced step gets
+    NaN for the first two and for ``gross_pitch_error``; so does the correlation of a constant track.  Plain torch in float64."""
+    if f0_a.dim() != 2 or f0_b.dim() != 2 or f0_a.shape != voiced_a.shape or f0_b.shape != voiced_b.shape \
+            or f0_a.shape[0] != f0_b.shape[0]:
+        raise ValueError("f0_metrics: expected (B, Ta) and (B, Tb) tracks with flags of their shapes, got %s %s %s %s"
+                         % (tuple(f0_a.shape), tuple(voiced_a.shape), tuple(f0_b.shape), tuple(voiced_b.shape)))
+    B, Ta = f0_a.shape
+    Tb = f0_b.shape[1]
+    dev = f0_a.device
+    la = torch.tensor(_lengths(len_a, B, Ta, "f0_metrics: len_a: ", full=Ta), device=dev)
+    lb = torch.tensor(_lengths(len_b, B, Tb, "f0_metrics: len_b: ", full=Tb), device=dev)
+    if path is None:
+        n = torch.minimum(la, lb)
+        idx = torch.arange(int(n.max()), device=dev)[None, :].expand(B, -1)
+        ia, ib, valid = idx, idx, idx < n[:, None]
+    else:
+        if path.dim() != 3 or path.shape[0] != B or path.shape[2] != 2:
+            raise ValueError("f0_metrics: expected a (B, L, 2) path, got %s" % (tuple(path.shape),))
+        ia, ib = path[..., 0].long(), path[..., 1].long()
+        valid = (ia >= 0) & (ib >= 0) & (ia < la[:, None]) & (ib < lb[:, None])
+        if steps is not None:
+            valid &= torch.arange(path.shape[1], device=dev)[None, :] < torch.as_tensor(steps, device=dev).long()[:, None]
+    ia, ib = ia.clamp(0, Ta - 1), ib.clamp(0, Tb - 1)
+    fa, fb = f0_a.double().gather(1, ia), f0_b.double().gather(1, ib)
+    va, vb = voiced_a.bool().gather(1, ia) & valid, voiced_b.bool().gather(1, ib) & valid
+    both = va & vb
+    nb = both.sum(1)
+    nan = torch.full((B,), float('nan'), dtype=torch.float64, device=dev)
+    one = torch.ones((), dtype=torch.float64, device=dev)
+    ra, rb = torch.where(both, fa, one), torch.where(both, fb, one)
+    cents = 1200.0 * torch.log2(ra / rb)
+    cnt = nb.clamp(min=1).double()
+    rmse = torch.sqrt((cents * cents).sum(1) / cnt)
+    gross = (both & ((ra / rb - 1.0).abs() > 0.2)).sum(1).double() / cnt
+    w = both.double()
+    ca, cb = (fa - ((fa * w).sum(1) / cnt)[:, None]) * w, (fb - ((fb * w).sum(1) / cnt)[:, None]) * w
+    corr = (ca * cb).sum(1) / torch.sqrt((ca * ca).sum(1) * (cb * cb).sum(1))          # 0 / 0 = NaN for a constant track
+    some = nb > 0
+    return {"f0_rmse_cents": torch.where(some, rmse, nan), "f0_corr": torch.where(some, corr, nan),
+            "vuv_error": ((va != vb) & valid).sum(1).double() / valid.sum(1).clamp(min=1).double(),
+            "gross_pitch_error": torch.where(some, gross, nan), "voiced_steps": nb}
+
+
 def precompute_mels(filelist, hparams, out_dir, out_filelist=None, resample=False):
     """Run every wav of a ``path|text`` filelist through the GPU front end once and write
     ``<out_dir>/<stem>.npy`` (n_mel, frames) float32 — the files the reference's

@@ -291,6 +291,7 @@ SYMBOLS = [
     "t2amd_stft_loss_sum_f32",
     "t2amd_resample_plan", "t2amd_resample_fwd_f32", "t2amd_resample_bwd_f32",
     "t2amd_dtw_width", "t2amd_mel_cepstrum_f32", "t2amd_dtw_f32", "t2amd_dtw_backtrack",
+    "t2amd_yin_plan", "t2amd_yin_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
@@ -413,6 +414,8 @@ def _argtypes():
         "t2amd_mel_cepstrum_f32": [_P, _L, _L, _P, _I, _I, _I, _P, _I, _P, _P],
         "t2amd_dtw_f32": [_P, _L, _P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P],
         "t2amd_dtw_backtrack": [_P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P],
+        "t2amd_yin_plan": [C.c_double, _I, _I, C.c_double, C.c_double, pt(C.c_int), pt(C.c_int)],
+        "t2amd_yin_f32": [_P, _L, _P, _I, _L, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P],
         "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
         "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
@@ -1892,6 +1895,32 @@ def dtw_backtrack(slab, na, nb, steps, Ta, Tb, out):
     _check(load().t2amd_dtw_backtrack(ps, rows, cols, _pair_lengths("dtw_backtrack", na, B), _pair_lengths("dtw_backtrack", nb, B),
                                       ptr(_fullc(steps), torch.int32), B, int(Ta), int(Tb), ptr(_fullc(out), torch.int32),
                                       int(out.shape[1]), _stream()), "t2amd_dtw_backtrack")
+
+
+# ---- F0 extraction by YIN (csrc/yin.hip) -------------------------------------------------------------------------------------------
+def yin_plan(sr, frame_length, hop_length, fmin, fmax):
+    """-> (tau_min, tau_max) = (floor(sr / fmax), ceil(sr / fmin)) of a YIN geometry; NativeError where the library refuses it."""
+    lo, hi = C.c_int(0), C.c_int(0)
+    _check(load().t2amd_yin_plan(float(sr), int(frame_length), int(hop_length), float(fmin), float(fmax), C.byref(lo), C.byref(hi)),
+           "t2amd_yin_plan")
+    return lo.value, hi.value
+
+
+def yin(x, lengths, frame_length, hop_length, tau_min, tau_max, sr, threshold, f0, voiced, aperiodicity, dprime=None):
+    """f0, aperiodicity (B, frames) float32 and voiced (B, frames) uint8 of the signals x (B, T) (unit stride along T), frames =
+    T // hop_length + 1, zeros at and beyond the ``lengths[b] // hop_length + 1`` frames of utterance b (device int32 or None);
+    ``dprime`` (B, frames, tau_max + 2) float32 receives d'(0 .. tau_max + 1) when given."""
+    px, ldx, B, T = _mat(x)
+    frames = T // max(int(hop_length), 1) + 1
+    for name, t, dt in (("f0", f0, torch.float32), ("voiced", voiced, torch.uint8), ("aperiodicity", aperiodicity, torch.float32)):
+        if tuple(t.shape) != (B, frames) or t.dtype != dt:
+            raise NativeError("yin: %s must be a (%d, %d) %s tensor, got %s %s" % (name, B, frames, dt, tuple(t.shape), t.dtype))
+    if dprime is not None and tuple(dprime.shape) != (B, frames, int(tau_max) + 2):
+        raise NativeError("yin: the d' slab must be (%d, %d, %d), got %s" % (B, frames, int(tau_max) + 2, tuple(dprime.shape)))
+    _check(load().t2amd_yin_f32(px, _i64(ldx), _pair_lengths("yin", lengths, B), B, _i64(T), frames, int(frame_length),
+                                int(hop_length), int(tau_min), int(tau_max), float(sr), float(threshold), ptr(_fullc(f0)),
+                                ptr(_fullc(voiced), torch.uint8), ptr(_fullc(aperiodicity)),
+                                None if dprime is None else ptr(_fullc(dprime)), _stream()), "t2amd_yin_f32")
 
 
 # ----------------------------------------------------------------------------
