@@ -1012,6 +1012,23 @@ int t2amd_yin_f32(const float* x, long long ldx, const int* lengths, int B, long
                   int tau_max, float sr, float threshold, float* f0, unsigned char* voiced, float* aperiodicity, float* dprime,
                   void* stream);
 
+/* Forced alignment: the best monotonic path through a (frames, tokens) score matrix (csrc/align.hip).  No
+ * atomics, one writer per element. */
+/* *width = lanes of the workgroup, *max_frames = 4096, *max_tokens = 1024. */
+int t2amd_align_limits(int* width, int* max_frames, int* max_tokens);
+/* *bytes = the workspace of a launch over B utterances of at most T_max frames and N_max tokens: one byte per cell at a row of
+ * N_max rounded up to 4, then two 64-bit counts of the 100 MHz clock per utterance (the recurrence, the backtrack). */
+int t2amd_align_workspace(int B, int T_max, int N_max, long long* bytes);
+/* scores[b * sb + t * st + n], t < t_len[b] <= T_max <= 4096, n < n_len[b] <= N_max <= 1024 (device int32; the host has refused
+ * every utterance without 1 <= n_len <= t_len).  Q(0,0) = l(0,0), Q(0,n>0) = -inf, Q(t,n) = l(t,n) + max(Q(t-1,n), Q(t-1,n-1)),
+ * staying wins ties; the path runs from (0,0) to (t_len-1, n_len-1) in steps of 0 or 1 tokens a frame.  durations (B, N_max)
+ * int32: frames on each token, zeros at and beyond n_len[b]; score (B,) = Q(t_len-1, n_len-1); path (NULL: not wanted)
+ * (B, T_max) int32: the token of every frame, -1 at and beyond t_len[b].  ws: ws_bytes >= t2amd_align_workspace's, 8-byte
+ * aligned; of utterance b's slab only rows 1 .. t_len-1 and columns below n_len rounded up to 4 are written. */
+int t2amd_monotonic_align_f32(const float* scores, long long sb, long long st, const int* t_len, const int* n_len, int B, int T_max,
+                              int N_max, int* durations, float* score, int* path, unsigned char* ws, long long ws_bytes,
+                              void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
  * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are

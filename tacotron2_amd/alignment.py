@@ -1,0 +1,104 @@
+"""Forced alignment on the GPU: the best monotonic path through a (frames, tokens) score matrix (csrc/align.hip, DESIGN.md
+section 18; Glow-TTS's "monotonic alignment search"), per-token durations from a Tacotron 2 attention matrix, and what the
+attention did beside that path.
+
+    durations, score = monotonic_align(scores, t_lengths, n_lengths)
+    durations, score, path = attention_durations(alignments, input_lengths, output_lengths, return_path=True)
+    metrics = alignment_metrics(alignments, path, input_lengths, output_lengths)
+
+Nothing here has a gradient, and there is no CPU path."""
+import numpy as np
+import torch
+
+from . import native as nv
+from .audio import _lengths, _require_device
+
+MAX_FRAMES = 4096
+MAX_TOKENS = 1024
+METRIC_KEYS = ("focus", "path_mass", "off_path", "backward_steps", "max_duration")
+
+
+@torch.no_grad()
+def monotonic_align(scores, t_lengths=None, n_lengths=None, return_path=False):
+    """The admissible path n(0) = 0, n(T-1) = N-1, n(t) - n(t-1) in {0, 1} of greatest summed score through each utterance of
+    the float32 device tensor ``scores`` (B, T, N) or (T, N): Q(t,n) = scores(t,n) + max(Q(t-1,n), Q(t-1,n-1)) in float32, staying
+    wins ties.  ``t_lengths`` / ``n_lengths`` are the frames and tokens of every utterance (the buffer's own where None); each
+    utterance needs 1 <= N <= T, T <= 4096, N <= 1024.  -> ``durations`` (B, N) int32, the frames on each token (zeros at and
+    beyond an utterance's N; a row sums to its T), ``score`` (B,) float32 = Q(T-1, N-1), and with ``return_path`` also ``path``
+    (B, T) int32, the token of every frame (-1 at and beyond T)."""
+    if not torch.is_tensor(scores) or scores.dtype != torch.float32:
+        raise TypeError("monotonic_align: expected a float32 tensor, got %s"
+                        % (scores.dtype if torch.is_tensor(scores) else type(scores).__name__))
+    if scores.dim() == 2:
+        scores = scores.unsqueeze(0)
+    if scores.dim() != 3 or min(scores.shape) < 1:
+        raise ValueError("monotonic_align: expected (B, T, N) or (T, N) scores, got shape %s" % (tuple(scores.shape),))
+    _require_device(scores)
+    scores = scores.detach()
+    B, T, N = scores.shape
+    tl = _lengths(t_lengths, B, None, "monotonic_align: t_", full=T)
+    nl = _lengths(n_lengths, B, None, "monotonic_align: n_", full=N)
+    for b in range(B):
+        if not (1 <= tl[b] <= T and 1 <= nl[b] <= N):
+            raise ValueError("monotonic_align: utterance %d: %d frames and %d tokens do not lie in [1, %d] and [1, %d]"
+                             % (b, tl[b], nl[b], T, N))
+        if tl[b] > MAX_FRAMES or nl[b] > MAX_TOKENS:
+            raise ValueError("monotonic_align: utterance %d: %d frames and %d tokens exceed the limits of %d frames and %d tokens"
+                             % (b, tl[b], nl[b], MAX_FRAMES, MAX_TOKENS))
+        if nl[b] > tl[b]:
+            raise ValueError("monotonic_align: utterance %d has %d tokens and only %d frames; a monotonic path needs 1 <= N <= T"
+                             % (b, nl[b], tl[b]))
+    Tm, Nm = max(tl), max(nl)
+    dev = scores.device
+    s = scores[:, :Tm, :Nm]
+    if Nm > 1 and s.stride(2) != 1:
+        s = s.contiguous()
+    t_dev, n_dev = (torch.tensor(v, dtype=torch.int32).to(dev) for v in (tl, nl))
+    durations = torch.empty(B, Nm, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    path = torch.empty(B, Tm, dtype=torch.int32, device=dev) if return_path else None
+    ws = torch.empty(nv.align_workspace(B, Tm, Nm), dtype=torch.uint8, device=dev)
+    nv.monotonic_align(s, t_dev, n_dev, durations, score, path, ws)
+    if Nm < N:                                                              # a longer buffer holding shorter utterances
+        durations = torch.nn.functional.pad(durations, (0, N - Nm))
+    if return_path and Tm < T:
+        path = torch.nn.functional.pad(path, (0, T - Tm), value=-1)
+    return (durations, score, path) if return_path else (durations, score)
+
+
+@torch.no_grad()
+def attention_durations(alignments, input_lengths, output_lengths, eps=1e-8, return_path=False):
+    """Per-token durations from the attention matrix ``alignments`` (B, To, Ti) that ``Tacotron2.forward`` and ``.inference``
+    return: ``monotonic_align`` of log(max(alignments, eps)) with ``output_lengths`` frames and ``input_lengths`` tokens."""
+    if not torch.is_tensor(alignments):
+        raise TypeError("attention_durations: expected a tensor, got %s" % type(alignments).__name__)
+    return monotonic_align(torch.log(alignments.detach().float().clamp_min(eps)), output_lengths, input_lengths, return_path)
+
+
+def alignment_metrics(alignments, path, input_lengths, output_lengths):
+    """What the attention ``alignments`` (B, To, Ti) did beside the monotonic ``path`` (B, To), per utterance, in float64 on the
+    host ("argmax" is the lowest index among the maxima) -> a dict of (B,) float64 arrays:
+    ``focus`` the mean over frames of max_n A; ``path_mass`` the mean over frames of A[t, path[t]]; ``off_path`` the share of
+    frames whose argmax is not path[t]; ``backward_steps`` the count of frames t >= 1 whose argmax lies below the previous
+    frame's; ``max_duration`` the largest number of frames on one token of the path."""
+    A = alignments.detach().double().cpu().numpy() if torch.is_tensor(alignments) else np.asarray(alignments, dtype=np.float64)
+    P = path.detach().cpu().numpy() if torch.is_tensor(path) else np.asarray(path)
+    if A.ndim == 2:
+        A, P = A[None], P[None] if P.ndim == 1 else P
+    if A.ndim != 3 or P.shape != A.shape[:2]:
+        raise ValueError("alignment_metrics: expected (B, To, Ti) alignments and a (B, To) path, got %s and %s" % (A.shape, P.shape))
+    B = A.shape[0]
+    ni = _lengths(input_lengths, B, A.shape[2], "alignment_metrics: input_", full=A.shape[2])
+    no = _lengths(output_lengths, B, A.shape[1], "alignment_metrics: output_", full=A.shape[1])
+    out = {k: np.zeros(B, dtype=np.float64) for k in METRIC_KEYS}
+    for b in range(B):
+        a, p = A[b, :no[b], :ni[b]], P[b, :no[b]].astype(np.int64)
+        if p.min() < 0 or p.max() >= ni[b]:
+            raise ValueError("alignment_metrics: the path of utterance %d leaves its %d tokens" % (b, ni[b]))
+        top = a.argmax(axis=1)
+        out["focus"][b] = a.max(axis=1).mean()
+        out["path_mass"][b] = a[np.arange(no[b]), p].mean()
+        out["off_path"][b] = (top != p).mean()
+        out["backward_steps"][b] = (top[1:] < top[:-1]).sum()
+        out["max_duration"][b] = np.bincount(p).max()
+    return out

@@ -292,6 +292,7 @@ SYMBOLS = [
     "t2amd_resample_plan", "t2amd_resample_fwd_f32", "t2amd_resample_bwd_f32",
     "t2amd_dtw_width", "t2amd_mel_cepstrum_f32", "t2amd_dtw_f32", "t2amd_dtw_backtrack",
     "t2amd_yin_plan", "t2amd_yin_f32",
+    "t2amd_align_limits", "t2amd_align_workspace", "t2amd_monotonic_align_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
@@ -416,6 +417,9 @@ def _argtypes():
         "t2amd_dtw_backtrack": [_P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P],
         "t2amd_yin_plan": [C.c_double, _I, _I, C.c_double, C.c_double, pt(C.c_int), pt(C.c_int)],
         "t2amd_yin_f32": [_P, _L, _P, _I, _L, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P],
+        "t2amd_align_limits": [pt(C.c_int), pt(C.c_int), pt(C.c_int)],
+        "t2amd_align_workspace": [_I, _I, _I, pt(C.c_longlong)],
+        "t2amd_monotonic_align_f32": [_P, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P],
         "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
         "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
@@ -1921,6 +1925,43 @@ def yin(x, lengths, frame_length, hop_length, tau_min, tau_max, sr, threshold, f
                                 int(hop_length), int(tau_min), int(tau_max), float(sr), float(threshold), ptr(_fullc(f0)),
                                 ptr(_fullc(voiced), torch.uint8), ptr(_fullc(aperiodicity)),
                                 None if dprime is None else ptr(_fullc(dprime)), _stream()), "t2amd_yin_f32")
+
+
+# ---- forced alignment: the best monotonic path (csrc/align.hip) ------------------------------------------------------------------
+def align_limits():
+    """-> (lanes of the workgroup, frames at most, tokens at most) of ``monotonic_align``."""
+    w, t, n = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(load().t2amd_align_limits(C.byref(w), C.byref(t), C.byref(n)), "t2amd_align_limits")
+    return w.value, t.value, n.value
+
+
+def align_workspace(B, T_max, N_max):
+    """Bytes of the workspace ``monotonic_align`` needs for B utterances of at most T_max frames and N_max tokens."""
+    n = C.c_longlong(0)
+    _check(load().t2amd_align_workspace(int(B), int(T_max), int(N_max), C.byref(n)), "t2amd_align_workspace")
+    return n.value
+
+
+def monotonic_align(scores, t_len, n_len, durations, score, path, ws):
+    """durations (B, N) int32, score (B,) float32 and, unless None, path (B, T) int32 of the best monotonic path through each
+    scores[b, :t_len[b], :n_len[b]] of the (B, T, N) float32 ``scores`` (unit stride along N; device int32 lengths); ``ws`` is a
+    uint8 tensor of at least ``align_workspace(B, T, N)`` bytes."""
+    if scores.dim() != 3 or min(scores.shape) < 1 or (scores.shape[2] > 1 and scores.stride(2) != 1):
+        raise NativeError("monotonic_align: expected (B, T, N) scores with unit stride along N, got shape %s stride %s"
+                          % (tuple(scores.shape), scores.stride()))
+    B, T, N = scores.shape
+    st = scores.stride(1) if T > 1 else max(scores.stride(1), N)
+    sb = scores.stride(0) if B > 1 else max(scores.stride(0), (T - 1) * st + N)
+    if tuple(durations.shape) != (B, N) or score.numel() != B or (path is not None and tuple(path.shape) != (B, T)):
+        raise NativeError("monotonic_align: expected durations (%d, %d), score (%d,) and path (%d, %d), got %s, %s and %s"
+                          % (B, N, B, B, T, tuple(durations.shape), tuple(score.shape), None if path is None else tuple(path.shape)))
+    if ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise NativeError("monotonic_align: the workspace must be a contiguous uint8 tensor, got %s" % ws.dtype)
+    _check(load().t2amd_monotonic_align_f32(ptr(scores), _i64(sb), _i64(st), _pair_lengths("monotonic_align", t_len, B),
+                                            _pair_lengths("monotonic_align", n_len, B), B, T, N,
+                                            ptr(_fullc(durations), torch.int32), ptr(_fullc(score)),
+                                            None if path is None else ptr(_fullc(path), torch.int32), ptr(ws, torch.uint8),
+                                            _i64(ws.numel()), _stream()), "t2amd_monotonic_align_f32")
 
 
 # ----------------------------------------------------------------------------
