@@ -1029,6 +1029,27 @@ int t2amd_monotonic_align_f32(const float* scores, long long sb, long long st, c
                               int N_max, int* durations, float* score, int* path, unsigned char* ws, long long ws_bytes,
                               void* stream);
 
+/* Forward-sum alignment likelihood and its gradient over the same paths (csrc/forward_sum.hip):
+ * a(0,0) = l(0,0), a(0,n>0) = -inf, a(t,n) = l(t,n) + logaddexp(a(t-1,n), a(t-1,n-1)), log Z = a(t_len-1, n_len-1); b the same
+ * from the other end; gamma(t,n) = exp(a + b - log Z) = d log Z / d l(t,n).  logaddexp(-inf, -inf) = -inf; an utterance without
+ * a possible path has log Z = -inf and zero gamma.  Rows are kept relative to float64 offsets renewed every 16 rows.  Lengths
+ * and limits are those of t2amd_monotonic_align_f32.  No atomics, one writer per element. */
+/* *bytes = the workspace of a launch over B utterances: with `keep`, the alpha rows (float32, a row of N_max rounded up to 4)
+ * and one float64 offset per row; always, at its tail, two 64-bit counts of the 100 MHz clock per utterance (the alpha
+ * launch, the beta launch). */
+int t2amd_forward_sum_workspace(int B, int T_max, int N_max, int keep, long long* bytes);
+/* log_z (B,) float32.  keep != 0: the alpha rows and their offsets go to ws for t2amd_forward_sum_bwd_f32 (of utterance b's
+ * slab only rows below t_len and columns below n_len, rounded up to 4 where N_max > 256, are written).  ws: ws_bytes >=
+ * t2amd_forward_sum_workspace's for the same `keep`, 16-byte aligned. */
+int t2amd_forward_sum_f32(const float* scores, long long sb, long long st, const int* t_len, const int* n_len, int B, int T_max,
+                          int N_max, float* log_z, int keep, unsigned char* ws, long long ws_bytes, void* stream);
+/* grad[b * gb + t * gt + n] = scale[b] gamma(t,n) (scale NULL: 1) for t < T_max, n < N_max, exact zeros at t >= t_len or
+ * n >= n_len; soft (NULL: not wanted) (B, N_max) = sum_t gamma(t,n), zeros at and beyond n_len.  scores, lengths, log_z and ws
+ * are those of a t2amd_forward_sum_f32 call with keep != 0. */
+int t2amd_forward_sum_bwd_f32(const float* scores, long long sb, long long st, const int* t_len, const int* n_len, int B, int T_max,
+                              int N_max, const float* log_z, const float* scale, float* grad, long long gb, long long gt,
+                              float* soft, unsigned char* ws, long long ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
  * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are

@@ -1,12 +1,17 @@
 """Forced alignment on the GPU: the best monotonic path through a (frames, tokens) score matrix (csrc/align.hip, DESIGN.md
 section 18; Glow-TTS's "monotonic alignment search"), per-token durations from a Tacotron 2 attention matrix, and what the
-attention did beside that path.
+attention did beside that path; and the sum over all such paths (csrc/forward_sum.hip; the forward-sum
+alignment likelihood of "One TTS Alignment To Rule Them All") with its gradient, the posterior occupancy of every cell.
 
     durations, score = monotonic_align(scores, t_lengths, n_lengths)
     durations, score, path = attention_durations(alignments, input_lengths, output_lengths, return_path=True)
     metrics = alignment_metrics(alignments, path, input_lengths, output_lengths)
+    log_z = forward_sum(scores, t_lengths, n_lengths)                      # differentiable: d log_z / d scores = gamma
+    gamma, soft_durations, log_z = alignment_posterior(scores, t_lengths, n_lengths)
+    loss = ForwardSumLoss(reduction='mean', per_frame=False)(scores, t_lengths, n_lengths)
 
-Nothing here has a gradient, and there is no CPU path."""
+``monotonic_align``, ``attention_durations`` and ``alignment_metrics`` have no gradient; ``forward_sum`` and ``ForwardSumLoss``
+have one.  There is no CPU path."""
 import numpy as np
 import torch
 
@@ -102,3 +107,113 @@ def alignment_metrics(alignments, path, input_lengths, output_lengths):
         out["backward_steps"][b] = (top[1:] < top[:-1]).sum()
         out["max_duration"][b] = np.bincount(p).max()
     return out
+
+
+def _forward_sum_args(scores, t_lengths, n_lengths):
+    """The validation of ``monotonic_align`` under the prefix ``forward_sum:`` -> (scores as (B, T, N), frames, tokens)."""
+    if not torch.is_tensor(scores) or scores.dtype != torch.float32:
+        raise TypeError("forward_sum: expected a float32 tensor, got %s"
+                        % (scores.dtype if torch.is_tensor(scores) else type(scores).__name__))
+    if scores.dim() == 2:
+        scores = scores.unsqueeze(0)
+    if scores.dim() != 3 or min(scores.shape) < 1:
+        raise ValueError("forward_sum: expected (B, T, N) or (T, N) scores, got shape %s" % (tuple(scores.shape),))
+    _require_device(scores)
+    B, T, N = scores.shape
+    tl = _lengths(t_lengths, B, None, "forward_sum: t_", full=T)
+    nl = _lengths(n_lengths, B, None, "forward_sum: n_", full=N)
+    for b in range(B):
+        if not (1 <= tl[b] <= T and 1 <= nl[b] <= N):
+            raise ValueError("forward_sum: utterance %d: %d frames and %d tokens do not lie in [1, %d] and [1, %d]"
+                             % (b, tl[b], nl[b], T, N))
+        if tl[b] > MAX_FRAMES or nl[b] > MAX_TOKENS:
+            raise ValueError("forward_sum: utterance %d: %d frames and %d tokens exceed the limits of %d frames and %d tokens"
+                             % (b, tl[b], nl[b], MAX_FRAMES, MAX_TOKENS))
+        if nl[b] > tl[b]:
+            raise ValueError("forward_sum: utterance %d has %d tokens and only %d frames; a monotonic path needs 1 <= N <= T"
+                             % (b, nl[b], tl[b]))
+    return scores, tl, nl
+
+
+def _forward_sum_launch(scores, tl, nl, keep):
+    """The alpha launch over the longest utterance's part of ``scores`` -> (that part, device lengths, log_z, workspace)."""
+    B = scores.shape[0]
+    Tm, Nm = max(tl), max(nl)
+    dev = scores.device
+    s = scores.detach()[:, :Tm, :Nm]
+    if Nm > 1 and s.stride(2) != 1:
+        s = s.contiguous()
+    t_dev, n_dev = (torch.tensor(v, dtype=torch.int32).to(dev) for v in (tl, nl))
+    log_z = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = torch.empty(nv.forward_sum_workspace(B, Tm, Nm, keep), dtype=torch.uint8, device=dev)
+    nv.forward_sum(s, t_dev, n_dev, log_z, ws, keep)
+    return s, t_dev, n_dev, log_z, ws
+
+
+def _forward_sum_gamma(shape, s, t_dev, n_dev, log_z, scale, ws, soft):
+    """The beta launch -> scale times gamma at the buffer's own ``shape`` (zeros beyond the longest utterance)."""
+    B, Tm, Nm = s.shape
+    whole = tuple(shape) == (B, Tm, Nm)
+    grad = (torch.empty if whole else torch.zeros)(shape, dtype=torch.float32, device=s.device)
+    nv.forward_sum_backward(s, t_dev, n_dev, log_z, scale, grad[:, :Tm, :Nm], soft, ws)
+    return grad
+
+
+class _ForwardSum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, tl, nl, keep):
+        s, t_dev, n_dev, log_z, ws = _forward_sum_launch(scores, tl, nl, keep)
+        if keep:
+            ctx.shape = scores.shape
+            ctx.save_for_backward(s, t_dev, n_dev, log_z, ws)
+        return log_z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        s, t_dev, n_dev, log_z, ws = ctx.saved_tensors
+        return _forward_sum_gamma(ctx.shape, s, t_dev, n_dev, log_z, grad_output.float().contiguous(), ws, None), None, None, None
+
+
+def forward_sum(scores, t_lengths=None, n_lengths=None):
+    """``log_z`` (B,) float32: the log of the summed probability of all admissible paths (those of ``monotonic_align``) through
+    each utterance of the float32 device tensor ``scores`` (B, T, N) or (T, N): alpha(0,0) = scores(0,0), alpha(t,n) = scores(t,n)
+    + logaddexp(alpha(t-1,n), alpha(t-1,n-1)), log_z = alpha(T-1, N-1).  Lengths, limits and refusals are those of
+    ``monotonic_align``.  A score of -inf marks an impossible cell; an utterance without a possible path gives -inf.
+    Differentiable: the gradient with respect to ``scores`` is ``grad_output`` times the posterior occupancy gamma (zeros in the
+    padding).  Under ``no_grad``, or where ``scores`` does not require a gradient, nothing is kept for a backward pass."""
+    scores, tl, nl = _forward_sum_args(scores, t_lengths, n_lengths)
+    return _ForwardSum.apply(scores, tl, nl, torch.is_grad_enabled() and scores.requires_grad)
+
+
+@torch.no_grad()
+def alignment_posterior(scores, t_lengths=None, n_lengths=None):
+    """-> ``gamma`` (B, T, N) float32, the posterior probability that a path drawn in proportion to exp(its score) is on token n
+    at frame t (d log_z / d scores; a row within an utterance sums to 1, zeros in the padding), ``soft_durations`` (B, N) float32,
+    its column sums (the expected frames on each token; a row sums to the utterance's T), and ``log_z`` (B,) as ``forward_sum``
+    gives it.  An utterance without a possible path has zeros and -inf."""
+    scores, tl, nl = _forward_sum_args(scores, t_lengths, n_lengths)
+    s, t_dev, n_dev, log_z, ws = _forward_sum_launch(scores, tl, nl, True)
+    soft = torch.empty(s.shape[0], s.shape[2], dtype=torch.float32, device=s.device)
+    gamma = _forward_sum_gamma(scores.shape, s, t_dev, n_dev, log_z, None, ws, soft)
+    if s.shape[2] < scores.shape[2]:                                        # a longer buffer holding shorter utterances
+        soft = torch.nn.functional.pad(soft, (0, scores.shape[2] - s.shape[2]))
+    return gamma, soft, log_z
+
+
+class ForwardSumLoss(torch.nn.Module):
+    """-log_z of ``forward_sum`` per utterance, divided by the utterance's frames where ``per_frame``, then reduced by
+    ``reduction`` ('mean', 'sum' or 'none')."""
+
+    def __init__(self, reduction='mean', per_frame=False):
+        super().__init__()
+        if reduction not in ('mean', 'sum', 'none'):
+            raise ValueError("ForwardSumLoss: reduction must be 'mean', 'sum' or 'none', got %r" % (reduction,))
+        self.reduction, self.per_frame = reduction, bool(per_frame)
+
+    def forward(self, scores, t_lengths=None, n_lengths=None):
+        scores, tl, nl = _forward_sum_args(scores, t_lengths, n_lengths)
+        loss = -forward_sum(scores, tl, nl)
+        if self.per_frame:
+            loss = loss / torch.tensor(tl, dtype=torch.float32).to(loss.device)
+        return loss if self.reduction == 'none' else loss.mean() if self.reduction == 'mean' else loss.sum()

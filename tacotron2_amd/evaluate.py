@@ -2,7 +2,7 @@
 (``audio.MelCepstralDistortion``, csrc/dtw.hip).
 
     python -m tacotron2_amd.evaluate --mels DIR_A DIR_B [--n-coef 13] [--batch 16] [-o FILE]
-    python -m tacotron2_amd.evaluate --checkpoint CKPT --filelist FILE [--hparams name=value,...] [--batch 16] [--alignment] [-o FILE]
+    python -m tacotron2_amd.evaluate --checkpoint CKPT --filelist FILE [--hparams name=value,...] [--batch 16] [--alignment [--posterior]] [-o FILE]
     python -m tacotron2_amd.evaluate --wavs DIR_A DIR_B [--f0-min 60] [--f0-max 800] [--f0-threshold 0.1] [-o FILE]
 
 Directory mode pairs the ``.npy`` natural-log mels (n_mel, frames) of the two directories by file name; names present on one side
@@ -21,7 +21,10 @@ of the other three (pairs without voiced overlap left out) and the count of such
 ``--alignment`` (checkpoint mode) also takes the best monotonic path through the free-running decode's attention matrix
 (``alignment.attention_durations``) and appends focus, path mass, off-path share, backward steps and longest
 duration (``alignment.alignment_metrics``) to each line, their means and the count of decodes shorter than their text
-(``unalignable``) to the summary.  Without the flag every mode prints what it printed before."""
+(``unalignable``) to the summary.  ``--alignment --posterior`` also sums over all monotonic paths (``alignment.alignment_posterior``,
+DESIGN.md section 19): each line gains ``log_z / frames`` and ``(score - log_z) / frames``, the log posterior per frame of the best
+path, and the summary their means ``log_likelihood_per_frame_mean`` and ``path_log_posterior_per_frame_mean``.  Without the flags
+every mode prints what it printed before."""
 import argparse
 import json
 import os
@@ -92,7 +95,7 @@ def evaluate_directories(dir_a, dir_b, n_coef=13, batch=16, device='cuda'):
     return rows, summarise(rows, {"unmatched": only_a + only_b})
 
 
-def evaluate_checkpoint(checkpoint, filelist, hparams, n_coef=13, batch=16, alignment=False):
+def evaluate_checkpoint(checkpoint, filelist, hparams, n_coef=13, batch=16, alignment=False, posterior=False):
     from .data_utils import TextMelCollate, TextMelLoader
     from .train import _read_checkpoint, load_model
     model = load_model(hparams)
@@ -102,7 +105,7 @@ def evaluate_checkpoint(checkpoint, filelist, hparams, n_coef=13, batch=16, alig
     collate = TextMelCollate(hparams.n_frames_per_step)
     device = next(model.parameters()).device
     mcd = audio.MelCepstralDistortion(n_coef)
-    rows, hit_max, arows, unalignable = [], 0, [], 0
+    rows, hit_max, arows, unalignable, prows = [], 0, [], 0, []
     if alignment:
         from . import align
     for k in range(0, len(data), batch):
@@ -120,19 +123,23 @@ def evaluate_checkpoint(checkpoint, filelist, hparams, n_coef=13, batch=16, alig
         names = [os.path.basename(data.audiopaths_and_text[idx[j]][0]) for j in order]
         got = [(n,) + r for n, r in zip(names, score_batch(mcd, ma, mb, device))]
         if alignment:
-            keep, _, metrics = align.measure(outs[3], input_lengths.tolist(), [max(1, v) for v in got_len])
+            keep, _, metrics, *more = align.measure(outs[3], input_lengths.tolist(), [max(1, v) for v in got_len], posterior)
             found = dict(zip(keep, metrics))
+            if posterior:
+                prows += more[1]
+                tail = dict(zip(keep, (" %.4f %.4f" % p for p in more[1])))
             unalignable += len(idx) - len(keep)
             arows += [(names[j], 0, 0) + found[j] for j in keep]
             for j, (name, fa, fb, steps, db) in enumerate(got):
                 print("%s %d %d %d %.4f %s" % (name, fa, fb, steps, db,
-                                               "%.4f %.4f %.4f %d %d" % found[j] if j in found else "unalignable"))
+                                               "%.4f %.4f %.4f %d %d" % found[j] + (tail[j] if posterior else "")
+                                               if j in found else "unalignable"))
         else:
             _report(got)
         rows += got
     extra = {"hit_max_decoder_steps": hit_max}
     if alignment:
-        extra.update(align.summarise(arows, []))
+        extra.update(align.summarise(arows, [], prows if posterior else None))
         extra.pop("count")
         extra["unalignable"] = unalignable
     return rows, summarise(rows, extra)
@@ -212,6 +219,8 @@ def main(argv=None):
     ap.add_argument('--f0-max', type=float, default=800.0, help='highest F0 of --wavs, Hz')
     ap.add_argument('--f0-threshold', type=float, default=0.1, help="YIN's threshold on d' for --wavs")
     ap.add_argument('--alignment', action='store_true', help='with --checkpoint: alignment metrics of the decode\'s attention')
+    ap.add_argument('--posterior', action='store_true',
+                    help='with --alignment: log Z and the best path\'s log posterior per frame, summed over all monotonic paths')
     args = ap.parse_args(argv)
     if args.wavs is not None and (args.mels is not None or args.checkpoint is not None):
         ap.error("give one of --mels DIR_A DIR_B, --wavs DIR_A DIR_B or --checkpoint CKPT --filelist FILE")
@@ -221,6 +230,8 @@ def main(argv=None):
         ap.error("--batch must be positive")
     if args.alignment and args.checkpoint is None:
         ap.error("--alignment needs --checkpoint CKPT --filelist FILE")
+    if args.posterior and not args.alignment:
+        ap.error("--posterior needs --checkpoint CKPT --filelist FILE --alignment")
     if args.wavs is not None:
         if not args.f0_min < args.f0_max:
             ap.error("--f0-min must be below --f0-max")
@@ -232,7 +243,7 @@ def main(argv=None):
             ap.error("--checkpoint needs --filelist")
         from .hparams import create_hparams
         _, summary = evaluate_checkpoint(args.checkpoint, args.filelist, create_hparams(args.hparams), args.n_coef, args.batch,
-                                         args.alignment)
+                                         args.alignment, args.posterior)
     line = json.dumps(summary)
     print(line)
     if args.output:

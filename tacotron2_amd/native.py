@@ -293,6 +293,7 @@ SYMBOLS = [
     "t2amd_dtw_width", "t2amd_mel_cepstrum_f32", "t2amd_dtw_f32", "t2amd_dtw_backtrack",
     "t2amd_yin_plan", "t2amd_yin_f32",
     "t2amd_align_limits", "t2amd_align_workspace", "t2amd_monotonic_align_f32",
+    "t2amd_forward_sum_workspace", "t2amd_forward_sum_f32", "t2amd_forward_sum_bwd_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
@@ -420,6 +421,9 @@ def _argtypes():
         "t2amd_align_limits": [pt(C.c_int), pt(C.c_int), pt(C.c_int)],
         "t2amd_align_workspace": [_I, _I, _I, pt(C.c_longlong)],
         "t2amd_monotonic_align_f32": [_P, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P],
+        "t2amd_forward_sum_workspace": [_I, _I, _I, _I, pt(C.c_longlong)],
+        "t2amd_forward_sum_f32": [_P, _L, _L, _P, _P, _I, _I, _I, _P, _I, _P, _L, _P],
+        "t2amd_forward_sum_bwd_f32": [_P, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _L, _L, _P, _P, _L, _P],
         "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
         "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
@@ -1962,6 +1966,66 @@ def monotonic_align(scores, t_len, n_len, durations, score, path, ws):
                                             ptr(_fullc(durations), torch.int32), ptr(_fullc(score)),
                                             None if path is None else ptr(_fullc(path), torch.int32), ptr(ws, torch.uint8),
                                             _i64(ws.numel()), _stream()), "t2amd_monotonic_align_f32")
+
+
+# ---- forward-sum alignment likelihood and its gradient (csrc/forward_sum.hip) ---------------------------------------------------
+def forward_sum_workspace(B, T_max, N_max, keep=True):
+    """Bytes of the workspace ``forward_sum`` needs for B utterances of at most T_max frames and N_max tokens; with ``keep`` it
+    holds the alpha rows ``forward_sum_backward`` reads."""
+    n = C.c_longlong(0)
+    _check(load().t2amd_forward_sum_workspace(int(B), int(T_max), int(N_max), 1 if keep else 0, C.byref(n)),
+           "t2amd_forward_sum_workspace")
+    return n.value
+
+
+def _forward_sum_strides(who, x):
+    if x.dim() != 3 or min(x.shape) < 1 or (x.shape[2] > 1 and x.stride(2) != 1):
+        raise NativeError("%s: expected a (B, T, N) tensor with unit stride along N, got shape %s stride %s"
+                          % (who, tuple(x.shape), x.stride()))
+    B, T, N = x.shape
+    st = x.stride(1) if T > 1 else max(x.stride(1), N)
+    sb = x.stride(0) if B > 1 else max(x.stride(0), (T - 1) * st + N)
+    return sb, st
+
+
+def _forward_sum_ws(who, ws):
+    if ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise NativeError("%s: the workspace must be a contiguous uint8 tensor, got %s" % (who, ws.dtype))
+    return ptr(ws, torch.uint8), _i64(ws.numel())
+
+
+def forward_sum(scores, t_len, n_len, log_z, ws, keep=True):
+    """log_z (B,) float32 = the log of the summed probability of all monotonic paths through each scores[b, :t_len[b], :n_len[b]]
+    of the (B, T, N) float32 ``scores`` (unit stride along N; device int32 lengths); ``ws`` is a uint8 tensor of at least
+    ``forward_sum_workspace(B, T, N, keep)`` bytes, and with ``keep`` it leaves holding what ``forward_sum_backward`` reads."""
+    sb, st = _forward_sum_strides("forward_sum", scores)
+    B, T, N = scores.shape
+    if log_z.numel() != B:
+        raise NativeError("forward_sum: expected log_z (%d,), got %s" % (B, tuple(log_z.shape)))
+    pw, nw = _forward_sum_ws("forward_sum", ws)
+    _check(load().t2amd_forward_sum_f32(ptr(scores), _i64(sb), _i64(st), _pair_lengths("forward_sum", t_len, B),
+                                        _pair_lengths("forward_sum", n_len, B), B, T, N, ptr(_fullc(log_z)), 1 if keep else 0,
+                                        pw, nw, _stream()), "t2amd_forward_sum_f32")
+
+
+def forward_sum_backward(scores, t_len, n_len, log_z, scale, grad, soft, ws):
+    """grad (B, T, N) float32 (unit stride along N) = scale[b] (None: 1) times the posterior occupancy of every cell, zeros in an
+    utterance's padding, and, unless None, soft (B, N) float32 = its column sums; ``scores``, the lengths, ``log_z`` and ``ws``
+    are those of a ``forward_sum(..., keep=True)`` call."""
+    sb, st = _forward_sum_strides("forward_sum_backward", scores)
+    gb, gt = _forward_sum_strides("forward_sum_backward", grad)
+    B, T, N = scores.shape
+    if tuple(grad.shape) != (B, T, N) or log_z.numel() != B or (scale is not None and scale.numel() != B) \
+            or (soft is not None and tuple(soft.shape) != (B, N)):
+        raise NativeError("forward_sum_backward: expected grad (%d, %d, %d), log_z and scale (%d,) and soft (%d, %d), got %s, %s, %s "
+                          "and %s" % (B, T, N, B, B, N, tuple(grad.shape), tuple(log_z.shape),
+                                      None if scale is None else tuple(scale.shape), None if soft is None else tuple(soft.shape)))
+    pw, nw = _forward_sum_ws("forward_sum_backward", ws)
+    _check(load().t2amd_forward_sum_bwd_f32(ptr(scores), _i64(sb), _i64(st), _pair_lengths("forward_sum_backward", t_len, B),
+                                            _pair_lengths("forward_sum_backward", n_len, B), B, T, N, ptr(_fullc(log_z)),
+                                            None if scale is None else ptr(_fullc(scale)), ptr(grad), _i64(gb), _i64(gt),
+                                            None if soft is None else ptr(_fullc(soft)), pw, nw, _stream()),
+           "t2amd_forward_sum_bwd_f32")
 
 
 # ----------------------------------------------------------------------------
