@@ -1050,6 +1050,54 @@ int t2amd_forward_sum_bwd_f32(const float* scores, long long sb, long long st, c
                               int N_max, const float* log_z, const float* scale, float* grad, long long gb, long long gt,
                               float* soft, unsigned char* ws, long long ws_bytes, void* stream);
 
+/* Learned-aligner scores and their gradient (csrc/aligner.hip, csrc/aligner_rows.hip): per utterance b
+ * with t_len[b] frames and n_len[b] tokens (device int32, 1 <= t_len <= T_max <= 4096, 1 <= n_len <= N_max <= 1024), queries
+ * q (B, T_max, C) and keys k (B, N_max, C) contiguous float32, 1 <= C <= 512, temperature tau > 0:
+ *   z(t,n) = tau (2 q_t . k_n - |k_n|^2), lse(t) = log sum_{n < n_len} exp z(t,n), s(t,n) = z(t,n) - lse(t) + logp(t,n),
+ * -inf at t >= t_len or n >= n_len.  No atomics, one writer per element, sums in a fixed order. */
+/* *bytes = a workspace: which 0 the forward's (the key slab, a row of C rounded up to 32, and the key norms), 1 the same with
+ * the row logsumexp kept for the backward, 2 the backward's own (dz at a row of N_max rounded up to 32, both operands
+ * transposed, the column sums of dz). */
+int t2amd_aligner_workspace(int B, int T_max, int N_max, int C, int which, long long* bytes);
+/* Kp (B, N_max, C rounded up to 32) = k with zeros beyond C and in rows at and beyond n_len; kn (B, N_max) = |k_n|^2. */
+int t2amd_aligner_pack_keys_f32(const float* k, const int* n_len, int B, int N_max, int C, float* Kp, float* kn, void* stream);
+/* out (B, C, R_max rounded up to 32): out[b][c][r] = x[b][r][c] for r < lens[b], zeros beyond; x (B, R_max, C). */
+int t2amd_aligner_transpose_f32(const float* x, const int* lens, int B, int R_max, int C, float* out, void* stream);
+/* The row pass of the forward, in place: scores[b * sb + t * st + n] holds z inside every utterance and leaves holding s, -inf
+ * in the padding; logp (NULL: none) at (pb, pt); lse (NULL: not kept) (B, T_max), written below t_len. */
+int t2amd_aligner_rows_fwd_f32(float* scores, long long sb, long long st, const float* logp, long long pb, long long pt,
+                               const int* t_len, const int* n_len, int B, int T_max, int N_max, float* lse, void* stream);
+/* The row pass of the backward: dz (B, T_max, N_max rounded up to 32) holds z inside every utterance and leaves holding
+ * dz = g - exp(z - lse) sum_n g, zeros elsewhere; colsum (B, N_max) = sum_t dz (float64 sums, rounded once; zeros at and beyond
+ * n_len); dlogp (NULL: not wanted) at (db, dt) = g inside an utterance, zeros outside.  g at (gb, gt). */
+int t2amd_aligner_rows_bwd_f32(const float* g, long long gb, long long gt, const int* t_len, const int* n_len, int B, int T_max,
+                               int N_max, const float* lse, float* dz, float* colsum, float* dlogp, long long db, long long dt,
+                               void* stream);
+/* scores (at sb, st) = s.  keep != 0 leaves in ws what t2amd_aligner_scores_bwd_f32 reads.  ws: ws_bytes >=
+ * t2amd_aligner_workspace's for which = (keep != 0), 16-byte aligned.  q and k need no alignment: the query rows are
+ * fetched four at a time where C is a multiple of 4 and q starts on 16 bytes, one at a time otherwise, with the same bits. */
+int t2amd_aligner_scores_f32(const float* q, const float* k, const int* t_len, const int* n_len, int B, int T_max, int N_max, int C,
+                             float tau, const float* logp, long long pb, long long pt, float* scores, long long sb, long long st,
+                             int keep, unsigned char* ws, long long ws_bytes, void* stream);
+/* Given g = dL/ds at (gb, gt) (its padding is ignored): dq (B, T_max, C) and dk (B, N_max, C) contiguous, exact zeros in the
+ * padding; dlogp (NULL: not wanted) at (db, dt).  `kept` is the workspace of a t2amd_aligner_scores_f32 call with keep != 0 on the
+ * same operands, ws the backward's own (which = 2). */
+int t2amd_aligner_scores_bwd_f32(const float* q, const float* k, const int* t_len, const int* n_len, int B, int T_max, int N_max,
+                                 int C, float tau, const float* g, long long gb, long long gt, float* dq, float* dk, float* dlogp,
+                                 long long db, long long dt, const unsigned char* kept, long long kept_bytes, unsigned char* ws,
+                                 long long ws_bytes, void* stream);
+/* One product of t2amd_aligner_scores_bwd_f32 alone, on its operands and workspaces (for timing a product by itself; the
+ * backward calls it three times): which 1 z into the dz slab of ws, 2 dQ from the dz and KT slabs, 3 dK from the dz and QT slabs
+ * and the column sums.  dq may be NULL unless which is 2, dk unless it is 3. */
+int t2amd_aligner_product_f32(int which, const float* q, const float* k, const int* t_len, const int* n_len, int B, int T_max,
+                              int N_max, int C, float tau, float* dq, float* dk, const unsigned char* kept, long long kept_bytes,
+                              unsigned char* ws, long long ws_bytes, void* stream);
+/* out (B, T_max, N_max) contiguous: the beta-binomial log prior of frame t over the tokens, a = scaling (t + 1),
+ * b = scaling (t_len - t), m = n_len - 1: lgamma(m+1) - lgamma(n+1) - lgamma(m-n+1) + lbeta(n + a, m - n + b) - lbeta(a, b) in
+ * float64, rounded once; -inf in the padding. */
+int t2amd_beta_binomial_log_prior_f32(const int* t_len, const int* n_len, int B, int T_max, int N_max, double scaling, float* out,
+                                      void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
  * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are

@@ -1,7 +1,9 @@
 """Forced alignment on the GPU: the best monotonic path through a (frames, tokens) score matrix (csrc/align.hip, DESIGN.md
 section 18; Glow-TTS's "monotonic alignment search"), per-token durations from a Tacotron 2 attention matrix, and what the
 attention did beside that path; and the sum over all such paths (csrc/forward_sum.hip; the forward-sum
-alignment likelihood of "One TTS Alignment To Rule Them All") with its gradient, the posterior occupancy of every cell.
+alignment likelihood of "One TTS Alignment To Rule Them All") with its gradient, the posterior occupancy of every cell; and the
+scores a learned aligner feeds both with (csrc/aligner.hip, csrc/aligner_rows.hip): the distances between
+projected frames and projected tokens, normalised over the tokens, plus a beta-binomial prior, with their gradient.
 
     durations, score = monotonic_align(scores, t_lengths, n_lengths)
     durations, score, path = attention_durations(alignments, input_lengths, output_lengths, return_path=True)
@@ -9,9 +11,12 @@ alignment likelihood of "One TTS Alignment To Rule Them All") with its gradient,
     log_z = forward_sum(scores, t_lengths, n_lengths)                      # differentiable: d log_z / d scores = gamma
     gamma, soft_durations, log_z = alignment_posterior(scores, t_lengths, n_lengths)
     loss = ForwardSumLoss(reduction='mean', per_frame=False)(scores, t_lengths, n_lengths)
+    scores = aligner_scores(queries, keys, t_lengths, n_lengths, temperature=0.0005, log_prior=None)   # differentiable
+    log_prior = beta_binomial_log_prior(t_lengths, n_lengths, scaling=1.0)
+    scores = AlignerScores(temperature=0.0005, prior_scaling=1.0)(queries, keys, t_lengths, n_lengths)
 
-``monotonic_align``, ``attention_durations`` and ``alignment_metrics`` have no gradient; ``forward_sum`` and ``ForwardSumLoss``
-have one.  There is no CPU path."""
+``monotonic_align``, ``attention_durations``, ``alignment_metrics`` and ``beta_binomial_log_prior`` have no gradient;
+``forward_sum``, ``ForwardSumLoss``, ``aligner_scores`` and ``AlignerScores`` have one.  There is no CPU path."""
 import numpy as np
 import torch
 
@@ -20,6 +25,7 @@ from .audio import _lengths, _require_device
 
 MAX_FRAMES = 4096
 MAX_TOKENS = 1024
+MAX_CHANNELS = 512
 METRIC_KEYS = ("focus", "path_mass", "off_path", "backward_steps", "max_duration")
 
 
@@ -217,3 +223,138 @@ class ForwardSumLoss(torch.nn.Module):
         if self.per_frame:
             loss = loss / torch.tensor(tl, dtype=torch.float32).to(loss.device)
         return loss if self.reduction == 'none' else loss.mean() if self.reduction == 'mean' else loss.sum()
+
+
+def _aligner_lengths(who, t_lengths, n_lengths, B, T, N):
+    tl = _lengths(t_lengths, B, None, who + ": t_", full=T)
+    nl = _lengths(n_lengths, B, None, who + ": n_", full=N)
+    for b in range(B):
+        if not (1 <= tl[b] <= T and 1 <= nl[b] <= N):
+            raise ValueError("%s: utterance %d: %d frames and %d tokens do not lie in [1, %d] and [1, %d]"
+                             % (who, b, tl[b], nl[b], T, N))
+    if T > MAX_FRAMES or N > MAX_TOKENS:
+        raise ValueError("%s: %d frames and %d tokens exceed the limits of %d frames and %d tokens" % (who, T, N, MAX_FRAMES, MAX_TOKENS))
+    return tl, nl
+
+
+def _dense_rows(x):
+    """``x`` (B, T, N) as the kernels take it: unit stride along N and row and batch strides that cover the matrix (an expanded
+    or transposed tensor is copied)."""
+    B, T, N = x.shape
+    ok = x.stride(2) == 1 and (T == 1 or x.stride(1) >= N) and (B == 1 or x.stride(0) >= (T - 1) * max(x.stride(1), N) + N)
+    return x if ok else x.contiguous()
+
+
+class _AlignerScores(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, logp, tl, nl, tau, keep):
+        B, T, C = q.shape
+        N = k.shape[1]
+        dev = q.device
+        qd, kd = q.detach().contiguous(), k.detach().contiguous()
+        lp = None if logp is None else _dense_rows(logp.detach())
+        t_dev, n_dev = (torch.tensor(v, dtype=torch.int32).to(dev) for v in (tl, nl))
+        scores = torch.empty(B, T, N, dtype=torch.float32, device=dev)
+        ws = torch.empty(nv.aligner_workspace(B, T, N, C, 1 if keep else 0), dtype=torch.uint8, device=dev)
+        nv.aligner_scores(qd, kd, t_dev, n_dev, tau, lp, scores, ws, keep)
+        if keep:
+            ctx.tau = tau
+            ctx.save_for_backward(qd, kd, t_dev, n_dev, ws)
+        return scores
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        q, k, t_dev, n_dev, kept = ctx.saved_tensors
+        B, T, C = q.shape
+        N = k.shape[1]
+        g = _dense_rows(grad.float())
+        dq, dk = torch.empty_like(q), torch.empty_like(k)
+        dlogp = torch.empty(B, T, N, dtype=torch.float32, device=q.device) if ctx.needs_input_grad[2] else None
+        ws = torch.empty(nv.aligner_workspace(B, T, N, C, 2), dtype=torch.uint8, device=q.device)
+        nv.aligner_scores_backward(q, k, t_dev, n_dev, ctx.tau, g, dq, dk, dlogp, kept, ws)
+        return dq, dk, dlogp, None, None, None, None
+
+
+def aligner_scores(queries, keys, t_lengths=None, n_lengths=None, temperature=0.0005, log_prior=None):
+    """``scores`` (B, T, N) float32 of a learned aligner: s(t,n) = z(t,n) - log sum_{n'} exp z(t,n') + log_prior(t,n) with
+    z(t,n) = -temperature |q_t - k_n|^2, the sum over the utterance's own tokens, -inf at and beyond an utterance's frames and
+    tokens, so that ``exp(scores)`` without a prior is an attention map.  ``queries`` (B, T, C) or (T, C) and ``keys`` (B, N, C) or
+    (N, C) are float32 device tensors, channel-last, 1 <= C <= 512, T <= 4096, N <= 1024 (more tokens than frames are allowed
+    here; the path functions refuse them); ``log_prior`` is None or a float32 (B, T, N) device tensor, -inf allowed
+    (``beta_binomial_log_prior``).  Differentiable once with respect to all three; exact zeros in the padding.  Under ``no_grad``,
+    or where no input requires a gradient, nothing is kept."""
+    who = "aligner_scores"
+    for name, t in (("queries", queries), ("keys", keys)) + ((("log_prior", log_prior),) if log_prior is not None else ()):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise TypeError("%s: expected float32 %s, got %s" % (who, name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if queries.dim() == 2 and keys.dim() == 2:
+        queries, keys = queries.unsqueeze(0), keys.unsqueeze(0)
+        if log_prior is not None and log_prior.dim() == 2:
+            log_prior = log_prior.unsqueeze(0)
+    if queries.dim() != 3 or keys.dim() != 3 or min(queries.shape) < 1 or min(keys.shape) < 1 \
+            or queries.shape[0] != keys.shape[0] or queries.shape[2] != keys.shape[2]:
+        raise ValueError("%s: expected queries (B, T, C) or (T, C) and keys (B, N, C) or (N, C), got shapes %s and %s"
+                         % (who, tuple(queries.shape), tuple(keys.shape)))
+    B, T, C = queries.shape
+    N = keys.shape[1]
+    if C > MAX_CHANNELS:
+        raise ValueError("%s: %d channels exceed the limit of %d" % (who, C, MAX_CHANNELS))
+    if log_prior is not None and tuple(log_prior.shape) != (B, T, N):
+        raise ValueError("%s: expected a log_prior of shape (%d, %d, %d), got %s" % (who, B, T, N, tuple(log_prior.shape)))
+    if not (isinstance(temperature, (int, float)) and 0.0 < float(temperature) < float("inf")):
+        raise ValueError("%s: the temperature must be a positive number, got %r" % (who, temperature))
+    tl, nl = _aligner_lengths(who, t_lengths, n_lengths, B, T, N)
+    for name, t in (("queries", queries), ("keys", keys), ("log_prior", log_prior)):
+        if t is not None:
+            _require_device(t)
+            if t.device != queries.device:
+                raise ValueError("%s: queries are on %s and %s on %s" % (who, queries.device, name, t.device))
+    keep = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (queries, keys, log_prior))
+    return _AlignerScores.apply(queries, keys, log_prior, tl, nl, float(temperature), keep)
+
+
+@torch.no_grad()
+def beta_binomial_log_prior(t_lengths, n_lengths, scaling=1.0, T=None, N=None, device=None):
+    """``log_prior`` (B, T, N) float32: for frame t of an utterance of T_b frames and N_b tokens the log of the beta-binomial
+    distribution over the tokens n = 0 .. N_b - 1 with m = N_b - 1 trials, a = scaling (t + 1), b = scaling (T_b - t), evaluated
+    in float64 and rounded once; every row sums to 1, one token gives 0, the padding holds -inf.  ``T`` / ``N`` default to the
+    longest utterance's, ``device`` to the current one."""
+    who = "beta_binomial_log_prior"
+    tl = _lengths(t_lengths, len(t_lengths) if hasattr(t_lengths, "__len__") else 0, None, who + ": t_")
+    nl = _lengths(n_lengths, len(tl), None, who + ": n_")
+    if not tl:
+        raise ValueError("%s: expected the frames and tokens of at least one utterance" % who)
+    T, N = (max(tl) if T is None else int(T)), (max(nl) if N is None else int(N))
+    tl, nl = _aligner_lengths(who, tl, nl, len(tl), T, N)
+    if not (isinstance(scaling, (int, float)) and 0.0 < float(scaling) <= 1e6):
+        raise ValueError("%s: the scaling must lie in (0, 1e6], got %r" % (who, scaling))
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None and not nv.validate_only() else torch.device(device or "cpu")
+    out = torch.empty(len(tl), T, N, dtype=torch.float32, device=dev)
+    _require_device(out)
+    t_dev, n_dev = (torch.tensor(v, dtype=torch.int32).to(dev) for v in (tl, nl))
+    nv.beta_binomial_log_prior(t_dev, n_dev, float(scaling), out)
+    return out
+
+
+class AlignerScores(torch.nn.Module):
+    """``aligner_scores`` at a fixed ``temperature``, with the beta-binomial prior of ``prior_scaling`` added where that is set.
+    It holds no weights: the encoders that make queries and keys are the caller's."""
+
+    def __init__(self, temperature=0.0005, prior_scaling=None):
+        super().__init__()
+        if not (isinstance(temperature, (int, float)) and 0.0 < float(temperature) < float("inf")):
+            raise ValueError("AlignerScores: the temperature must be a positive number, got %r" % (temperature,))
+        if prior_scaling is not None and not (isinstance(prior_scaling, (int, float)) and 0.0 < float(prior_scaling) <= 1e6):
+            raise ValueError("AlignerScores: prior_scaling must be None or lie in (0, 1e6], got %r" % (prior_scaling,))
+        self.temperature, self.prior_scaling = float(temperature), prior_scaling
+
+    def forward(self, queries, keys, t_lengths=None, n_lengths=None):
+        prior = None
+        if self.prior_scaling is not None and torch.is_tensor(queries) and torch.is_tensor(keys) and queries.dim() == keys.dim() \
+                and queries.dim() in (2, 3):
+            B = 1 if queries.dim() == 2 else queries.shape[0]
+            T, N = queries.shape[-2], keys.shape[-2]
+            tl, nl = _aligner_lengths("aligner_scores", t_lengths, n_lengths, B, T, N)
+            prior = beta_binomial_log_prior(tl, nl, self.prior_scaling, T, N, queries.device)
+        return aligner_scores(queries, keys, t_lengths, n_lengths, self.temperature, prior)

@@ -294,6 +294,9 @@ SYMBOLS = [
     "t2amd_yin_plan", "t2amd_yin_f32",
     "t2amd_align_limits", "t2amd_align_workspace", "t2amd_monotonic_align_f32",
     "t2amd_forward_sum_workspace", "t2amd_forward_sum_f32", "t2amd_forward_sum_bwd_f32",
+    "t2amd_aligner_workspace", "t2amd_aligner_pack_keys_f32", "t2amd_aligner_transpose_f32", "t2amd_aligner_rows_fwd_f32",
+    "t2amd_aligner_rows_bwd_f32", "t2amd_aligner_scores_f32", "t2amd_aligner_scores_bwd_f32", "t2amd_aligner_product_f32",
+    "t2amd_beta_binomial_log_prior_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
@@ -424,6 +427,15 @@ def _argtypes():
         "t2amd_forward_sum_workspace": [_I, _I, _I, _I, pt(C.c_longlong)],
         "t2amd_forward_sum_f32": [_P, _L, _L, _P, _P, _I, _I, _I, _P, _I, _P, _L, _P],
         "t2amd_forward_sum_bwd_f32": [_P, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _L, _L, _P, _P, _L, _P],
+        "t2amd_aligner_workspace": [_I, _I, _I, _I, _I, pt(C.c_longlong)],
+        "t2amd_aligner_pack_keys_f32": [_P, _P, _I, _I, _I, _P, _P, _P],
+        "t2amd_aligner_transpose_f32": [_P, _P, _I, _I, _I, _P, _P],
+        "t2amd_aligner_rows_fwd_f32": [_P, _L, _L, _P, _L, _L, _P, _P, _I, _I, _I, _P, _P],
+        "t2amd_aligner_rows_bwd_f32": [_P, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _P],
+        "t2amd_aligner_scores_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _L, _L, _P, _L, _L, _I, _P, _L, _P],
+        "t2amd_aligner_scores_bwd_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _L, _L, _P, _P, _P, _L, _L, _P, _L, _P, _L, _P],
+        "t2amd_aligner_product_f32": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _L, _P, _L, _P],
+        "t2amd_beta_binomial_log_prior_f32": [_P, _P, _I, _I, _I, C.c_double, _P, _P],
         "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
         "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
@@ -2026,6 +2038,70 @@ def forward_sum_backward(scores, t_len, n_len, log_z, scale, grad, soft, ws):
                                             None if scale is None else ptr(_fullc(scale)), ptr(grad), _i64(gb), _i64(gt),
                                             None if soft is None else ptr(_fullc(soft)), pw, nw, _stream()),
            "t2amd_forward_sum_bwd_f32")
+
+
+# ---- learned-aligner scores and their gradient (csrc/aligner.hip, csrc/aligner_rows.hip) ------------------------------------------
+def aligner_workspace(B, T_max, N_max, C_, which=0):
+    """Bytes of a workspace of the aligner scores for B utterances of at most T_max frames and N_max tokens of C_ channels:
+    ``which`` 0 the forward's, 1 the forward's with what the backward reads kept, 2 the backward's own."""
+    n = C.c_longlong(0)
+    _check(load().t2amd_aligner_workspace(int(B), int(T_max), int(N_max), int(C_), int(which), C.byref(n)), "t2amd_aligner_workspace")
+    return n.value
+
+
+def _aligner_operands(who, q, k):
+    if q.dim() != 3 or k.dim() != 3 or min(q.shape) < 1 or min(k.shape) < 1 or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
+        raise NativeError("%s: expected queries (B, T, C) and keys (B, N, C), got %s and %s" % (who, tuple(q.shape), tuple(k.shape)))
+    return q.shape[0], q.shape[1], k.shape[1], q.shape[2]
+
+
+def aligner_scores(q, k, t_len, n_len, tau, log_prior, scores, ws, keep=False):
+    """scores (B, T, N) float32 (unit stride along N) = log_softmax over the tokens of -tau |q_t - k_n|^2, plus ``log_prior``
+    (B, T, N) or None, -inf in every utterance's padding; q (B, T, C) and k (B, N, C) contiguous float32, device int32 lengths;
+    ``ws`` is a uint8 tensor of at least ``aligner_workspace(B, T, N, C, keep)`` bytes, and with ``keep`` it leaves holding what
+    ``aligner_scores_backward`` reads."""
+    B, T, N, C_ = _aligner_operands("aligner_scores", q, k)
+    if tuple(scores.shape) != (B, T, N) or (log_prior is not None and tuple(log_prior.shape) != (B, T, N)):
+        raise NativeError("aligner_scores: expected scores and log_prior (%d, %d, %d), got %s and %s"
+                          % (B, T, N, tuple(scores.shape), None if log_prior is None else tuple(log_prior.shape)))
+    sb, st = _forward_sum_strides("aligner_scores", scores)
+    pb, pt = (0, 0) if log_prior is None else _forward_sum_strides("aligner_scores", log_prior)
+    pw, nw = _forward_sum_ws("aligner_scores", ws)
+    _check(load().t2amd_aligner_scores_f32(ptr(_fullc(q)), ptr(_fullc(k)), _pair_lengths("aligner_scores", t_len, B),
+                                           _pair_lengths("aligner_scores", n_len, B), B, T, N, C_, float(tau), ptr(log_prior),
+                                           _i64(pb), _i64(pt), ptr(scores), _i64(sb), _i64(st), 1 if keep else 0, pw, nw, _stream()),
+           "t2amd_aligner_scores_f32")
+
+
+def aligner_scores_backward(q, k, t_len, n_len, tau, grad, dq, dk, dlogp, kept, ws):
+    """dq (B, T, C), dk (B, N, C) contiguous float32 and, unless None, dlogp (B, T, N) from ``grad`` = dL/dscores (B, T, N) (unit
+    stride along N), exact zeros in every utterance's padding; ``kept`` is the workspace of an ``aligner_scores(..., keep=True)``
+    call on the same operands, ``ws`` a uint8 tensor of at least ``aligner_workspace(B, T, N, C, 2)`` bytes."""
+    B, T, N, C_ = _aligner_operands("aligner_scores_backward", q, k)
+    if tuple(grad.shape) != (B, T, N) or tuple(dq.shape) != (B, T, C_) or tuple(dk.shape) != (B, N, C_) \
+            or (dlogp is not None and tuple(dlogp.shape) != (B, T, N)):
+        raise NativeError("aligner_scores_backward: expected grad and dlogp (%d, %d, %d), dq (%d, %d, %d) and dk (%d, %d, %d), got "
+                          "%s, %s, %s and %s" % (B, T, N, B, T, C_, B, N, C_, tuple(grad.shape),
+                                                 None if dlogp is None else tuple(dlogp.shape), tuple(dq.shape), tuple(dk.shape)))
+    gb, gt = _forward_sum_strides("aligner_scores_backward", grad)
+    db, dt = (0, 0) if dlogp is None else _forward_sum_strides("aligner_scores_backward", dlogp)
+    pk, nk = _forward_sum_ws("aligner_scores_backward", kept)
+    pw, nw = _forward_sum_ws("aligner_scores_backward", ws)
+    _check(load().t2amd_aligner_scores_bwd_f32(ptr(_fullc(q)), ptr(_fullc(k)), _pair_lengths("aligner_scores_backward", t_len, B),
+                                               _pair_lengths("aligner_scores_backward", n_len, B), B, T, N, C_, float(tau), ptr(grad),
+                                               _i64(gb), _i64(gt), ptr(_fullc(dq)), ptr(_fullc(dk)), ptr(dlogp), _i64(db), _i64(dt),
+                                               pk, nk, pw, nw, _stream()), "t2amd_aligner_scores_bwd_f32")
+
+
+def beta_binomial_log_prior(t_len, n_len, scaling, out):
+    """out (B, T, N) contiguous float32 = the beta-binomial log prior of every frame over the tokens of utterance b (device int32
+    lengths), evaluated in float64 and rounded once; -inf in the padding."""
+    if out.dim() != 3 or min(out.shape) < 1:
+        raise NativeError("beta_binomial_log_prior: expected a (B, T, N) tensor, got %s" % (tuple(out.shape),))
+    B, T, N = out.shape
+    _check(load().t2amd_beta_binomial_log_prior_f32(_pair_lengths("beta_binomial_log_prior", t_len, B),
+                                                    _pair_lengths("beta_binomial_log_prior", n_len, B), B, T, N, float(scaling),
+                                                    ptr(_fullc(out)), _stream()), "t2amd_beta_binomial_log_prior_f32")
 
 
 # ----------------------------------------------------------------------------
