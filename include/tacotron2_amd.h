@@ -1098,6 +1098,36 @@ int t2amd_aligner_product_f32(int which, const float* q, const float* k, const i
 int t2amd_beta_binomial_log_prior_f32(const int* t_len, const int* n_len, int B, int T_max, int N_max, double scaling, float* out,
                                       void* stream);
 
+/* The length regulator (csrc/regulate.hip): per utterance b with n_len[b] tokens (device int32, clamped
+ * into [0, N_max]; NULL: N_max) and durations d(n) >= 0, e(n) = d(0) + .. + d(n) (64-bit, a term counts as at most 2^31 - 1),
+ * S = e(n_len - 1), T_b = min(S, T); path(t) = the smallest n < n_len with e(n) > t for t < T_b and -1 for T_b <= t < T.
+ * 1 <= B <= 65535, 1 <= N_max <= 1024, T <= 65536, 1 <= C <= 512.  No atomics, one writer per element, sums in a fixed order. */
+/* *max_channels = 512, *max_tokens = 1024, *max_frames = 65536. */
+int t2amd_regulate_limits(int* max_channels, int* max_tokens, int* max_frames);
+/* durations[b * db + n], int32 (duration_bytes 4) or int64 (8); those at and beyond n_len[b] are not read.  t_lengths (B,) = T_b;
+ * path (NULL: not wanted) (B, T) int32; ends (NULL: not wanted) (B, N_max) int32 = min(e(n), T), T_b at and beyond n_len;
+ * totals (NULL: not wanted) (B,) int64 = S.  T may be 0.  An utterance with a negative duration below n_len is marked:
+ * t_lengths = -1, totals = -1, ends 0, path -1. */
+int t2amd_durations_to_path_i32(const void* durations, int duration_bytes, long long db, const int* n_len, int B, int N_max, int T,
+                                int* path, int* t_lengths, int* ends, long long* totals, void* stream);
+/* y (B, T, C) contiguous: y(t, :) = x(path(t), :), +0 where path(t) = -1; x[b * xb + n * xn + c].  Rows move 16 bytes at a
+ * time where C is a multiple of 4, x and y start on 16 bytes and the strides are multiples of 4, one float at a time
+ * otherwise, with the same bits.  1 <= T. */
+int t2amd_length_regulate_f32(const float* x, long long xb, long long xn, const int* path, int B, int N_max, int T, int C, float* y,
+                              void* stream);
+/* dx (B, N_max, C) contiguous: dx(n, :) = the sum of dy(t, :) over t = ends(n-1) .. ends(n) - 1 ascending (ends(-1) = 0), plain
+ * float32 adds from the first term, +0 for an empty range; dy[b * gb + t * gt + c]; ends as t2amd_durations_to_path_i32 wrote. */
+int t2amd_length_regulate_bwd_f32(const float* dy, long long gb, long long gt, const int* ends, int B, int N_max, int T, int C,
+                                  float* dx, void* stream);
+/* Over the same ranges: num(n, c) = fmaf(w(t), v(t, c), num) from +0, den(n) = den + w(t) from +0 (w NULL: 1), m = num / den where
+ * den > 0 and +0 elsewhere.  v[b * vb + t * vt + c], w[b * wb + t]; m and num (NULL: not wanted) (B, N_max, C), den (B, N_max). */
+int t2amd_token_average_f32(const float* v, long long vb, long long vt, const float* w, long long wb, const int* ends, int B,
+                            int N_max, int T, int C, float* m, float* den, float* num, void* stream);
+/* dv (B, T, C) contiguous: dv(t, c) = w(t) * (g(path(t), c) / den(path(t))), +0 where path(t) = -1 or den = 0; g (B, N_max, C)
+ * and den (B, N_max) contiguous. */
+int t2amd_token_average_bwd_f32(const float* g, const float* den, const float* w, long long wb, const int* path, int B, int N_max,
+                                int T, int C, float* dv, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
  * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are

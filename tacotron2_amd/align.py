@@ -2,6 +2,7 @@
 (``alignment.attention_durations``, csrc/align.hip).
 
     python -m tacotron2_amd.align --checkpoint CKPT --filelist FILE -o DIR [--hparams name=value,...] [--batch 16] [--posterior]
+                                  [--token-features]
 
 Builds the model and the data set the way ``evaluate.evaluate_checkpoint`` does, runs the teacher-forced
 ``model(model.parse_batch(batch))`` in eval mode under ``no_grad`` and takes the best monotonic path through the log of the
@@ -15,7 +16,15 @@ csrc/forward_sum.hip): it writes ``DIR/NAME.soft.npy`` (fl
 ``NAME.npy``, appends ``log_z / frames`` and ``(score - log_z) / frames`` to each utterance's line (the latter is the log posterior
 per frame of the path whose durations were written, <= 0 up to rounding: near 0 means the hard durations can be trusted) and adds
 their means, ``log_likelihood_per_frame_mean`` and ``path_log_posterior_per_frame_mean``, to the summary.  Without the flag output
-and summary are what they were."""
+and summary are what they were.
+
+``--token-features`` also writes the per-token prosody targets of a duration-based acoustic model beside ``NAME.npy``
+(``alignment.token_average``, csrc/regulate.hip): ``DIR/NAME.energy.npy`` (float32, the mean over each
+token's frames of the frame energy, the L2 norm over the mel channels of exp(log-mel)) and, where the loader reads wavs (neither
+``synthetic:`` nor ``load_mel_from_disk``), ``DIR/NAME.f0.npy`` (float32 Hz, the mean of ``audio.yin``'s track at the mel's hop
+over each token's voiced frames, 0 for a token without one); otherwise it prints one line saying that pitch is skipped.  The
+summary gains ``energy_mean`` (over all tokens) and, with pitch, ``f0_voiced_token_share``.  Without the flag output and summary
+are what they were."""
 import argparse
 import json
 import os
@@ -71,7 +80,32 @@ def measure(alignments, input_lengths, output_lengths, with_posterior=False):
     return out + posterior(A, ki, ko, score) if with_posterior else out
 
 
-def align_checkpoint(checkpoint, filelist, hparams, out_dir, batch=16, with_posterior=False):
+def token_features(mel, durations, wavs=None, hparams=None):
+    """Per-token energy, and with ``wavs`` (one (samples,) float tensor in [-1, 1] per utterance) per-token F0, of a batch: ``mel``
+    (B, n_mel, To) log-mel on the device, ``durations`` a list of int rows.  -> ([float32 energy rows], [float32 F0 rows] or
+    None)."""
+    from . import audio
+    dev, ni = mel.device, [len(d) for d in durations]
+    dmat = torch.zeros(len(ni), max(ni), dtype=torch.int32)
+    for j, d in enumerate(durations):
+        dmat[j, :ni[j]] = torch.from_numpy(np.asarray(d, dtype=np.int32))
+    dmat = dmat.to(dev)
+    energy = alignment.token_average(torch.exp(mel.float()).norm(dim=1).contiguous(), dmat, ni).cpu().numpy()
+    pitch = None
+    if wavs is not None:
+        To, lens = mel.shape[2], [int(w.numel()) for w in wavs]
+        y = torch.zeros(len(wavs), max(lens))
+        for j, w in enumerate(wavs):
+            y[j, :lens[j]] = w
+        f0, voiced, _ = audio.yin(y.to(dev), lens, sr=hparams.sampling_rate, frame_length=hparams.win_length,
+                                  hop_length=hparams.hop_length)
+        f0, voiced = (torch.nn.functional.pad(t.float(), (0, max(To - t.shape[1], 0)))[:, :To].contiguous() for t in (f0, voiced))
+        pitch = alignment.token_average(f0, dmat, ni, weights=voiced).cpu().numpy()
+    rows = lambda a: [a[j, :ni[j]].astype(np.float32) for j in range(len(ni))]                        # noqa: E731
+    return rows(energy), None if pitch is None else rows(pitch)
+
+
+def align_checkpoint(checkpoint, filelist, hparams, out_dir, batch=16, with_posterior=False, with_features=False):
     from .data_utils import TextMelCollate, TextMelLoader
     from .train import _read_checkpoint, load_model
     if hparams.n_frames_per_step != 1:
@@ -82,7 +116,10 @@ def align_checkpoint(checkpoint, filelist, hparams, out_dir, batch=16, with_post
     data = TextMelLoader(filelist, hparams)
     collate = TextMelCollate(hparams.n_frames_per_step)
     os.makedirs(out_dir, exist_ok=True)
-    rows, unalignable, post = [], [], []
+    rows, unalignable, post, energies, pitches = [], [], [], [], []
+    with_pitch = with_features and data.synthetic is None and not hparams.load_mel_from_disk
+    if with_features and not with_pitch:
+        print("token features: pitch is skipped, the loader reads no wavs (a synthetic: filelist or load_mel_from_disk)")
     for k in range(0, len(data), batch):
         idx = list(range(k, min(k + batch, len(data))))
         items = [data[i] for i in idx]
@@ -98,8 +135,20 @@ def align_checkpoint(checkpoint, filelist, hparams, out_dir, batch=16, with_post
             if j not in keep:
                 print("unalignable: %s %d %d" % (names[j], ni[j], no[j]))
                 unalignable.append(names[j])
+        if with_features and keep:
+            wavs = None
+            if with_pitch:
+                from .utils import load_wav_to_torch
+                wavs = [load_wav_to_torch(data.audiopaths_and_text[idx[order[j]]][0])[0] / hparams.max_wav_value for j in keep]
+            energy, pitch = token_features(b[2][keep].to(outs[3].device), durs, wavs, hparams)
         for k, (j, d, m) in enumerate(zip(keep, durs, metrics)):
             np.save(os.path.join(out_dir, names[j] + ".npy"), d.astype(np.int32))
+            if with_features:
+                np.save(os.path.join(out_dir, names[j] + ".energy.npy"), energy[k])
+                energies.append(energy[k])
+                if with_pitch:
+                    np.save(os.path.join(out_dir, names[j] + ".f0.npy"), pitch[k])
+                    pitches.append(pitch[k])
             row = (names[j], ni[j], no[j]) + m
             line = "%s %d %d %.4f %.4f %.4f %d %d" % row
             if with_posterior:
@@ -108,7 +157,12 @@ def align_checkpoint(checkpoint, filelist, hparams, out_dir, batch=16, with_post
                 post.append(more[1][k])
             print(line)
             rows.append(row)
-    return rows, summarise(rows, unalignable, post if with_posterior else None)
+    summary = summarise(rows, unalignable, post if with_posterior else None)
+    if with_features:
+        summary["energy_mean"] = float(np.concatenate(energies).mean()) if energies else None
+        if with_pitch:
+            summary["f0_voiced_token_share"] = float((np.concatenate(pitches) > 0).mean()) if pitches else None
+    return rows, summary
 
 
 def main(argv=None):
@@ -120,11 +174,14 @@ def main(argv=None):
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--posterior', action='store_true',
                     help='also write NAME.soft.npy (expected durations) and report log Z and the path\'s log posterior per frame')
+    ap.add_argument('--token-features', action='store_true',
+                    help='also write NAME.energy.npy and, where the loader reads wavs, NAME.f0.npy (per-token means)')
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error("--batch must be positive")
     from .hparams import create_hparams
-    _, summary = align_checkpoint(args.checkpoint, args.filelist, create_hparams(args.hparams), args.output, args.batch, args.posterior)
+    _, summary = align_checkpoint(args.checkpoint, args.filelist, create_hparams(args.hparams), args.output, args.batch, args.posterior,
+                                 args.token_features)
     line = json.dumps(summary)
     print(line)
     with open(os.path.join(args.output, "summary.json"), 'w') as fh:

@@ -3,7 +3,9 @@ section 18; Glow-TTS's "monotonic alignment search"), per-token durations from a
 attention did beside that path; and the sum over all such paths (csrc/forward_sum.hip; the forward-sum
 alignment likelihood of "One TTS Alignment To Rule Them All") with its gradient, the posterior occupancy of every cell; and the
 scores a learned aligner feeds both with (csrc/aligner.hip, csrc/aligner_rows.hip): the distances between
-projected frames and projected tokens, normalised over the tokens, plus a beta-binomial prior, with their gradient.
+projected frames and projected tokens, normalised over the tokens, plus a beta-binomial prior, with their gradient; and what
+consumes a duration (csrc/regulate.hip): the length regulator of FastSpeech and FastPitch, which repeats
+token n's vector d(n) times, and the mean of a frame-rate quantity over each token's frames, both with their gradients.
 
     durations, score = monotonic_align(scores, t_lengths, n_lengths)
     durations, score, path = attention_durations(alignments, input_lengths, output_lengths, return_path=True)
@@ -14,9 +16,14 @@ projected frames and projected tokens, normalised over the tokens, plus a beta-b
     scores = aligner_scores(queries, keys, t_lengths, n_lengths, temperature=0.0005, log_prior=None)   # differentiable
     log_prior = beta_binomial_log_prior(t_lengths, n_lengths, scaling=1.0)
     scores = AlignerScores(temperature=0.0005, prior_scaling=1.0)(queries, keys, t_lengths, n_lengths)
+    path, t_lengths = durations_to_path(durations, n_lengths, T=None)
+    y, t_lengths = length_regulate(x, durations, n_lengths, T=None)         # differentiable in x
+    y, t_lengths = LengthRegulator(pace=1.0, rounding=True, max_len=None)(x, durations, n_lengths)
+    per_token = token_average(values, durations, n_lengths, weights=None)   # differentiable in values
 
-``monotonic_align``, ``attention_durations``, ``alignment_metrics`` and ``beta_binomial_log_prior`` have no gradient;
-``forward_sum``, ``ForwardSumLoss``, ``aligner_scores`` and ``AlignerScores`` have one.  There is no CPU path."""
+``monotonic_align``, ``attention_durations``, ``alignment_metrics``, ``beta_binomial_log_prior`` and ``durations_to_path`` have no
+gradient; ``forward_sum``, ``ForwardSumLoss``, ``aligner_scores``, ``AlignerScores``, ``length_regulate``, ``LengthRegulator`` and
+``token_average`` have one.  There is no CPU path."""
 import numpy as np
 import torch
 
@@ -358,3 +365,235 @@ class AlignerScores(torch.nn.Module):
             tl, nl = _aligner_lengths("aligner_scores", t_lengths, n_lengths, B, T, N)
             prior = beta_binomial_log_prior(tl, nl, self.prior_scaling, T, N, queries.device)
         return aligner_scores(queries, keys, t_lengths, n_lengths, self.temperature, prior)
+
+
+# ---- the length regulator (csrc/regulate.hip) ----------------------------------------------------------------
+MAX_REGULATED_FRAMES = 65536
+
+
+def _regulate_args(who, durations, n_lengths, batch_of_one):
+    """``durations`` as (B, N) int32 or int64 with unit stride along N, and the token counts as a device int32 vector or None.
+    Token counts given on the host are checked against [0, N]; a device tensor is not read here, the kernel clamps it."""
+    if not torch.is_tensor(durations) or durations.dtype not in (torch.int32, torch.int64):
+        raise TypeError("%s: expected int32 or int64 durations, got %s"
+                        % (who, durations.dtype if torch.is_tensor(durations) else type(durations).__name__))
+    if batch_of_one and durations.dim() == 1:
+        durations = durations.unsqueeze(0)
+    if durations.dim() != 2 or min(durations.shape) < 1:
+        raise ValueError("%s: expected (B, N) or (N,) durations with at least one token, got shape %s" % (who, tuple(durations.shape)))
+    _require_device(durations)
+    B, N = durations.shape
+    if N > MAX_TOKENS:
+        raise ValueError("%s: %d tokens exceed the limit of %d" % (who, N, MAX_TOKENS))
+    durations = durations.detach()
+    if N > 1 and durations.stride(1) != 1 or (B > 1 and durations.stride(0) < N):
+        durations = durations.contiguous()
+    dev = durations.device
+    if n_lengths is None:
+        return durations, None
+    if torch.is_tensor(n_lengths) and n_lengths.device.type != "cpu":
+        if n_lengths.device != dev:
+            raise ValueError("%s: durations are on %s and n_lengths on %s" % (who, dev, n_lengths.device))
+        if n_lengths.dim() != 1 or n_lengths.numel() != B:
+            raise ValueError("%s: n_%d lengths for a batch of %d" % (who, n_lengths.numel(), B))
+        return durations, n_lengths.detach().to(torch.int32).contiguous()
+    nl = _lengths(n_lengths, B, None, who + ": n_")
+    for b in range(B):
+        if not 0 <= nl[b] <= N:
+            raise ValueError("%s: utterance %d: %d tokens do not lie in [0, %d]" % (who, b, nl[b], N))
+    return durations, torch.tensor(nl, dtype=torch.int32).to(dev)
+
+
+def _regulate_frames(who, durations, n_dev, T):
+    """The output's frame count: ``T`` itself, or with None the largest sum of the batch, by the call's one device-to-host read,
+    which also brings the sign check."""
+    if T is not None:
+        if isinstance(T, bool) or not isinstance(T, int) or not 0 <= T <= MAX_REGULATED_FRAMES:
+            raise ValueError("%s: T must be None or an int in [0, %d], got %r" % (who, MAX_REGULATED_FRAMES, T))
+        return T
+    B = durations.shape[0]
+    totals = torch.empty(B, dtype=torch.int64, device=durations.device)
+    nv.durations_to_path(durations, n_dev, 0, None, torch.empty(B, dtype=torch.int32, device=durations.device), None, totals)
+    lo, hi = torch.stack((totals.min(), totals.max())).tolist()             # the one read
+    if lo < 0:
+        raise ValueError("%s: negative durations" % who)
+    if hi > MAX_REGULATED_FRAMES:
+        raise ValueError("%s: durations sum to %d frames, more than the limit of %d; name T to cut them" % (who, hi, MAX_REGULATED_FRAMES))
+    return int(hi)
+
+
+def _paths(durations, n_dev, T, want_path, want_ends):
+    B, N = durations.shape
+    dev = durations.device
+    t_lengths = torch.empty(B, dtype=torch.int32, device=dev)
+    path = torch.empty(B, T, dtype=torch.int32, device=dev) if want_path else None
+    ends = torch.empty(B, N, dtype=torch.int32, device=dev) if want_ends else None
+    nv.durations_to_path(durations, n_dev, T, path, t_lengths, ends)
+    return path, t_lengths, ends
+
+
+@torch.no_grad()
+def durations_to_path(durations, n_lengths=None, T=None):
+    """The token of every frame under the int32 or int64 device tensor ``durations`` (B, N) or (N,), d >= 0: with e(n) = d(0) + ..
+    + d(n) over the utterance's ``n_lengths`` tokens (0 <= N_b <= N; all N where None; what lies beyond is ignored) and
+    T_b = min(e(N_b - 1), T), path(t) is the smallest n with e(n) > t for t < T_b and -1 from T_b on; a token of duration 0 owns no
+    frame.  -> ``path`` (B, T) int32 and ``t_lengths`` (B,) int32 = T_b.  For the durations ``monotonic_align`` returns this is the
+    path it returns.
+
+    With ``T=None`` the frame count is the largest sum of the batch, found by one device-to-host read (a synchronisation); the
+    same read refuses negative durations and sums above 65 536.  With ``T`` an int nothing is read back and the call does not
+    synchronise: longer utterances are cut at T, and an utterance with a negative duration is marked on the device instead of
+    refused: its ``t_lengths`` entry is -1 and it has no frames.  N <= 1024, T <= 65 536."""
+    who = "durations_to_path"
+    d, n_dev = _regulate_args(who, durations, n_lengths, True)
+    T = _regulate_frames(who, d, n_dev, T)
+    path, t_lengths, _ = _paths(d, n_dev, T, True, False)
+    return path, t_lengths
+
+
+def _regulate_grad(g):
+    """A gradient as the kernels take it: float32, unit stride along C, strides that cover the tensor (the expanded gradient of
+    ``.sum().backward()`` is copied)."""
+    return _dense_rows(g.float())
+
+
+class _LengthRegulate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, durations, n_dev, T, keep):
+        B, N, C = x.shape
+        path, t_lengths, ends = _paths(durations, n_dev, T, T > 0, keep)
+        y = torch.empty(B, T, C, dtype=torch.float32, device=x.device)
+        if T > 0:
+            nv.length_regulate(_dense_rows(x.detach()), path, y)
+        if keep:
+            ctx.save_for_backward(ends)
+        ctx.mark_non_differentiable(t_lengths)
+        return y, t_lengths
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad, _):
+        ends, = ctx.saved_tensors
+        B, T, C = grad.shape
+        if T == 0:
+            return torch.zeros(B, ends.shape[1], C, dtype=torch.float32, device=grad.device), None, None, None, None
+        dx = torch.empty(B, ends.shape[1], C, dtype=torch.float32, device=grad.device)
+        nv.length_regulate_backward(_regulate_grad(grad), ends, dx)
+        return dx, None, None, None, None
+
+
+def length_regulate(x, durations, n_lengths=None, T=None):
+    """The length regulator: token n's vector repeated d(n) times.  ``x`` is a float32 device tensor (B, N, C) or (N, C) (a batch
+    of one, with (N,) durations), 1 <= C <= 512; ``durations``, ``n_lengths`` and ``T`` are those of ``durations_to_path``.
+    -> ``y`` (B, T, C) float32 with y(t, :) = x(path(t), :) below the utterance's T_b and +0 from there on, and ``t_lengths`` (B,)
+    int32 = T_b.  It is a copy: every finite value, infinity, NaN and -0 keeps its bits.  Differentiable once with respect to
+    ``x``: dx(n, :) is the sum of dy(t, :) over the token's frames, t ascending, in plain float32 adds; +0 for a token without a
+    frame and at and beyond N_b; frames cut off by T contribute nothing.
+
+    With ``T=None`` the frame count is the largest sum of the batch, found by one device-to-host read (a synchronisation), which
+    also refuses negative durations; an all-zero batch gives T = 0 and an empty ``y``.  With ``T`` an int there is no
+    synchronisation anywhere in the call; an utterance with a negative duration then has ``t_lengths`` = -1 and a ``y`` of
+    zeros.  A non-contiguous ``x`` or gradient is made contiguous."""
+    who = "length_regulate"
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise TypeError("%s: expected a float32 tensor, got %s" % (who, x.dtype if torch.is_tensor(x) else type(x).__name__))
+    if x.dim() == 2 and torch.is_tensor(durations) and durations.dim() == 1:
+        x, durations = x.unsqueeze(0), durations.unsqueeze(0)
+    if x.dim() != 3 or min(x.shape) < 1:
+        raise ValueError("%s: expected (B, N, C) or (N, C) tokens, got shape %s" % (who, tuple(x.shape)))
+    _require_device(x)
+    if torch.is_tensor(durations) and durations.device != x.device:
+        raise ValueError("%s: the tokens are on %s and the durations on %s" % (who, x.device, durations.device))
+    d, n_dev = _regulate_args(who, durations, n_lengths, False)
+    if tuple(d.shape) != tuple(x.shape[:2]):
+        raise ValueError("%s: expected durations of shape %s, got %s" % (who, tuple(x.shape[:2]), tuple(d.shape)))
+    if x.shape[2] > MAX_CHANNELS:
+        raise ValueError("%s: %d channels exceed the limit of %d" % (who, x.shape[2], MAX_CHANNELS))
+    T = _regulate_frames(who, d, n_dev, T)
+    return _LengthRegulate.apply(x, d, n_dev, T, torch.is_grad_enabled() and x.requires_grad)
+
+
+class LengthRegulator(torch.nn.Module):
+    """``length_regulate`` with the frame count ``max_len`` (None: the batch's longest, one synchronisation).  Integer durations
+    pass through; float durations (a duration predictor's output at inference) become d = max(0, round(durations / pace)), or the
+    floor instead of the rounding where ``rounding`` is False, in one elementwise pass.  It holds no weights."""
+
+    def __init__(self, pace=1.0, rounding=True, max_len=None):
+        super().__init__()
+        if not (isinstance(pace, (int, float)) and 0.0 < float(pace) < float("inf")):
+            raise ValueError("LengthRegulator: the pace must be a positive number, got %r" % (pace,))
+        if max_len is not None and (isinstance(max_len, bool) or not isinstance(max_len, int) or not 0 <= max_len <= MAX_REGULATED_FRAMES):
+            raise ValueError("LengthRegulator: max_len must be None or an int in [0, %d], got %r" % (MAX_REGULATED_FRAMES, max_len))
+        self.pace, self.rounding, self.max_len = float(pace), bool(rounding), max_len
+
+    def forward(self, x, durations, n_lengths=None):
+        if torch.is_tensor(durations) and durations.is_floating_point():
+            d = durations.detach() / self.pace
+            durations = (torch.round(d) if self.rounding else torch.floor(d)).clamp_(0, 2147483647).to(torch.int32)
+        return length_regulate(x, durations, n_lengths, self.max_len)
+
+
+class _TokenAverage(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v, durations, n_dev, w, keep):
+        B, T, C = v.shape
+        N = durations.shape[1]
+        path, _, ends = _paths(durations, n_dev, T, keep, True)
+        vd = _dense_rows(v.detach())
+        mean = torch.empty(B, N, C, dtype=torch.float32, device=v.device)
+        den = torch.empty(B, N, dtype=torch.float32, device=v.device)
+        nv.token_average(vd, w, ends, mean, den)
+        if keep:
+            ctx.save_for_backward(path, den, w)
+        return mean
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        path, den, w = ctx.saved_tensors
+        dv = torch.empty(grad.shape[0], path.shape[1], grad.shape[2], dtype=torch.float32, device=grad.device)
+        nv.token_average_backward(grad.float().contiguous(), den, w, path, dv)
+        return dv, None, None, None, None
+
+
+def token_average(values, durations, n_lengths=None, weights=None):
+    """The mean of a frame-rate quantity over each token's frames.  ``values`` is a float32 device tensor (B, T) or (B, T, C),
+    1 <= C <= 512, T <= 65 536; its T is the frame count (durations that sum past it are cut there, as in ``durations_to_path``
+    with that T); ``durations`` (B, N) and ``n_lengths`` are those of ``durations_to_path``; ``weights`` is None (ones) or a
+    non-negative float32 device tensor (B, T).  With the token's frames t ascending, num = fmaf(w(t), v(t), num) and
+    den = den + w(t), both from +0, and the result is num / den where den > 0 and +0 elsewhere: a token without frames, or whose
+    frames all weigh 0 (the mean over the voiced frames, with the voiced flags as weights).  -> (B, N) or (B, N, C) float32.
+    Differentiable once with respect to ``values``: dv(t) = w(t) * (g(path(t)) / den(path(t))), +0 where den = 0 and beyond the
+    utterance's frames; ``weights`` gets no gradient.  The call never synchronises: an utterance with a negative duration is not
+    refused, it gives zeros."""
+    who = "token_average"
+    if not torch.is_tensor(values) or values.dtype != torch.float32:
+        raise TypeError("%s: expected float32 values, got %s" % (who, values.dtype if torch.is_tensor(values) else type(values).__name__))
+    if values.dim() not in (2, 3) or min(values.shape) < 1:
+        raise ValueError("%s: expected (B, T) or (B, T, C) values, got shape %s" % (who, tuple(values.shape)))
+    flat = values.dim() == 2
+    v = values.unsqueeze(2) if flat else values
+    B, T, C = v.shape
+    _require_device(v)
+    if T > MAX_REGULATED_FRAMES or C > MAX_CHANNELS:
+        raise ValueError("%s: %d frames and %d channels exceed the limits of %d frames and %d channels"
+                         % (who, T, C, MAX_REGULATED_FRAMES, MAX_CHANNELS))
+    if torch.is_tensor(durations) and durations.device != v.device:
+        raise ValueError("%s: the values are on %s and the durations on %s" % (who, v.device, durations.device))
+    d, n_dev = _regulate_args(who, durations, n_lengths, False)
+    if d.shape[0] != B:
+        raise ValueError("%s: expected durations (%d, N), got shape %s" % (who, B, tuple(d.shape)))
+    w = None
+    if weights is not None:
+        if not torch.is_tensor(weights) or weights.dtype != torch.float32:
+            raise TypeError("%s: expected float32 weights, got %s"
+                            % (who, weights.dtype if torch.is_tensor(weights) else type(weights).__name__))
+        if tuple(weights.shape) != (B, T):
+            raise ValueError("%s: expected weights of shape (%d, %d), got %s" % (who, B, T, tuple(weights.shape)))
+        if weights.device != v.device:
+            raise ValueError("%s: the values are on %s and the weights on %s" % (who, v.device, weights.device))
+        w = weights.detach()
+        if (T > 1 and w.stride(1) != 1) or (B > 1 and w.stride(0) < T):
+            w = w.contiguous()
+    mean = _TokenAverage.apply(v, d, n_dev, w, torch.is_grad_enabled() and values.requires_grad)
+    return mean.squeeze(2) if flat else mean

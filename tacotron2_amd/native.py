@@ -297,6 +297,8 @@ SYMBOLS = [
     "t2amd_aligner_workspace", "t2amd_aligner_pack_keys_f32", "t2amd_aligner_transpose_f32", "t2amd_aligner_rows_fwd_f32",
     "t2amd_aligner_rows_bwd_f32", "t2amd_aligner_scores_f32", "t2amd_aligner_scores_bwd_f32", "t2amd_aligner_product_f32",
     "t2amd_beta_binomial_log_prior_f32",
+    "t2amd_regulate_limits", "t2amd_durations_to_path_i32", "t2amd_length_regulate_f32", "t2amd_length_regulate_bwd_f32",
+    "t2amd_token_average_f32", "t2amd_token_average_bwd_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
@@ -436,6 +438,12 @@ def _argtypes():
         "t2amd_aligner_scores_bwd_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _L, _L, _P, _P, _P, _L, _L, _P, _L, _P, _L, _P],
         "t2amd_aligner_product_f32": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _L, _P, _L, _P],
         "t2amd_beta_binomial_log_prior_f32": [_P, _P, _I, _I, _I, C.c_double, _P, _P],
+        "t2amd_regulate_limits": [pt(C.c_int), pt(C.c_int), pt(C.c_int)],
+        "t2amd_durations_to_path_i32": [_P, _I, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+        "t2amd_length_regulate_f32": [_P, _L, _L, _P, _I, _I, _I, _I, _P, _P],
+        "t2amd_length_regulate_bwd_f32": [_P, _L, _L, _P, _I, _I, _I, _I, _P, _P],
+        "t2amd_token_average_f32": [_P, _L, _L, _P, _L, _P, _I, _I, _I, _I, _P, _P, _P, _P],
+        "t2amd_token_average_bwd_f32": [_P, _P, _P, _L, _P, _I, _I, _I, _I, _P, _P],
         "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
         "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
@@ -2102,6 +2110,118 @@ def beta_binomial_log_prior(t_len, n_len, scaling, out):
     _check(load().t2amd_beta_binomial_log_prior_f32(_pair_lengths("beta_binomial_log_prior", t_len, B),
                                                     _pair_lengths("beta_binomial_log_prior", n_len, B), B, T, N, float(scaling),
                                                     ptr(_fullc(out)), _stream()), "t2amd_beta_binomial_log_prior_f32")
+
+
+# ---- the length regulator: durations -> path, expansion, pooling and their gradients (csrc/regulate.hip) --------------------------
+def regulate_limits():
+    """-> (channels at most, tokens at most, frames at most) of the length regulator."""
+    c, n, t = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(load().t2amd_regulate_limits(C.byref(c), C.byref(n), C.byref(t)), "t2amd_regulate_limits")
+    return c.value, n.value, t.value
+
+
+def _regulate_rows(who, x, what):
+    """Strides (batch, row) of a (B, R, C) float32 tensor with unit stride along C."""
+    if x.dim() != 3 or min(x.shape) < 1 or (x.shape[2] > 1 and x.stride(2) != 1):
+        raise NativeError("%s: expected (B, rows, C) %s with unit stride along C, got shape %s stride %s"
+                          % (who, what, tuple(x.shape), x.stride()))
+    B, R, C_ = x.shape
+    sr = x.stride(1) if R > 1 else max(x.stride(1), C_)
+    sb = x.stride(0) if B > 1 else max(x.stride(0), (R - 1) * sr + C_)
+    return sb, sr
+
+
+def _regulate_ints(who, t, shape, name):
+    if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
+        raise NativeError("%s: expected contiguous int32 %s of shape %s, got %s %s" % (who, name, tuple(shape), t.dtype, tuple(t.shape)))
+    return None if t is None else ptr(t, torch.int32)
+
+
+def durations_to_path(durations, n_len, T, path, t_lengths, ends=None, totals=None):
+    """From the (B, N) int32 or int64 ``durations`` (unit stride along N) and the device int32 token counts ``n_len`` (None: N):
+    t_lengths (B,) int32 = min(sum of the durations, T) and, unless None, path (B, T) int32 (the token of every frame, -1 at and
+    beyond t_lengths), ends (B, N) int32 (the inclusive prefix sums clamped to T) and totals (B,) int64 (the sums themselves).
+    An utterance with a negative duration leaves with t_lengths = totals = -1 and no frames."""
+    who = "durations_to_path"
+    if durations.dim() != 2 or min(durations.shape) < 1 or (durations.shape[1] > 1 and durations.stride(1) != 1) \
+            or durations.dtype not in (torch.int32, torch.int64):
+        raise NativeError("%s: expected (B, N) int32 or int64 durations with unit stride along N, got %s shape %s stride %s"
+                          % (who, durations.dtype, tuple(durations.shape), durations.stride()))
+    B, N = durations.shape
+    db = durations.stride(0) if B > 1 else max(durations.stride(0), N)
+    if totals is not None and (totals.dtype != torch.int64 or tuple(totals.shape) != (B,) or not totals.is_contiguous()):
+        raise NativeError("%s: expected contiguous int64 totals of shape (%d,)" % (who, B))
+    _check(load().t2amd_durations_to_path_i32(ptr(durations, None), durations.element_size(), _i64(db), _pair_lengths(who, n_len, B),
+                                              B, N, int(T), _regulate_ints(who, path, (B, int(T)), "path"),
+                                              _regulate_ints(who, t_lengths, (B,), "t_lengths"), _regulate_ints(who, ends, (B, N), "ends"),
+                                              None if totals is None else ptr(totals, torch.int64), _stream()),
+           "t2amd_durations_to_path_i32")
+
+
+def length_regulate(x, path, y):
+    """y (B, T, C) contiguous float32: y[b, t] = x[b, path[b, t]], +0 where path is -1; x (B, N, C), unit stride along C."""
+    xb, xn = _regulate_rows("length_regulate", x, "tokens")
+    B, N, C_ = x.shape
+    if y.dim() != 3 or y.shape[0] != B or y.shape[2] != C_ or tuple(path.shape) != tuple(y.shape[:2]):
+        raise NativeError("length_regulate: expected y (%d, T, %d) and path (%d, T), got %s and %s"
+                          % (B, C_, B, tuple(y.shape), tuple(path.shape)))
+    T = y.shape[1]
+    _check(load().t2amd_length_regulate_f32(ptr(x), _i64(xb), _i64(xn), _regulate_ints("length_regulate", path, (B, T), "path"), B, N,
+                                            T, C_, ptr(_fullc(y)), _stream()), "t2amd_length_regulate_f32")
+
+
+def length_regulate_backward(dy, ends, dx):
+    """dx (B, N, C) contiguous float32: the sum of dy (B, T, C) (unit stride along C) over each token's frames, ascending; ``ends``
+    (B, N) int32 as ``durations_to_path`` wrote it."""
+    gb, gt = _regulate_rows("length_regulate_backward", dy, "gradient")
+    B, T, C_ = dy.shape
+    if dx.dim() != 3 or dx.shape[0] != B or dx.shape[2] != C_:
+        raise NativeError("length_regulate_backward: expected dx (%d, N, %d), got %s" % (B, C_, tuple(dx.shape)))
+    N = dx.shape[1]
+    _check(load().t2amd_length_regulate_bwd_f32(ptr(dy), _i64(gb), _i64(gt), _regulate_ints("length_regulate_backward", ends, (B, N), "ends"),
+                                                B, N, T, C_, ptr(_fullc(dx)), _stream()), "t2amd_length_regulate_bwd_f32")
+
+
+def _regulate_weights(who, w, B, T):
+    if w is None:
+        return None, 0
+    if w.dim() != 2 or tuple(w.shape) != (B, T) or (T > 1 and w.stride(1) != 1):
+        raise NativeError("%s: expected (%d, %d) weights with unit stride along T, got shape %s stride %s"
+                          % (who, B, T, tuple(w.shape), w.stride()))
+    return ptr(w), (w.stride(0) if B > 1 else max(w.stride(0), T))
+
+
+def token_average(values, weights, ends, mean, den, num=None):
+    """mean (B, N, C) and den (B, N) contiguous float32, and unless None num (B, N, C): the weighted sums of values (B, T, C) (unit
+    stride along C) over each token's frames, the sums of the weights (B, T) (None: ones), and their quotient (+0 where den = 0)."""
+    who = "token_average"
+    vb, vt = _regulate_rows(who, values, "values")
+    B, T, C_ = values.shape
+    if mean.dim() != 3 or mean.shape[0] != B or mean.shape[2] != C_ or tuple(den.shape) != tuple(mean.shape[:2]) \
+            or (num is not None and tuple(num.shape) != tuple(mean.shape)):
+        raise NativeError("%s: expected mean and num (%d, N, %d) and den (%d, N), got %s, %s and %s"
+                          % (who, B, C_, B, tuple(mean.shape), None if num is None else tuple(num.shape), tuple(den.shape)))
+    N = mean.shape[1]
+    pw, wb = _regulate_weights(who, weights, B, T)
+    _check(load().t2amd_token_average_f32(ptr(values), _i64(vb), _i64(vt), pw, _i64(wb), _regulate_ints(who, ends, (B, N), "ends"), B, N,
+                                          T, C_, ptr(_fullc(mean)), ptr(_fullc(den)), None if num is None else ptr(_fullc(num)),
+                                          _stream()), "t2amd_token_average_f32")
+
+
+def token_average_backward(grad, den, weights, path, dv):
+    """dv (B, T, C) contiguous float32 = weights[b, t] * (grad[b, path[b, t]] / den[b, path[b, t]]), +0 where path is -1 or den is 0;
+    grad (B, N, C) and den (B, N) contiguous."""
+    who = "token_average_backward"
+    if grad.dim() != 3 or dv.dim() != 3 or min(grad.shape) < 1 or min(dv.shape) < 1 or grad.shape[0] != dv.shape[0] \
+            or grad.shape[2] != dv.shape[2] or tuple(den.shape) != tuple(grad.shape[:2]):
+        raise NativeError("%s: expected grad (B, N, C), den (B, N) and dv (B, T, C), got %s, %s and %s"
+                          % (who, tuple(grad.shape), tuple(den.shape), tuple(dv.shape)))
+    B, N, C_ = grad.shape
+    T = dv.shape[1]
+    pw, wb = _regulate_weights(who, weights, B, T)
+    _check(load().t2amd_token_average_bwd_f32(ptr(_fullc(grad)), ptr(_fullc(den)), pw, _i64(wb),
+                                              _regulate_ints(who, path, (B, T), "path"), B, N, T, C_, ptr(_fullc(dv)), _stream()),
+           "t2amd_token_average_bwd_f32")
 
 
 # ----------------------------------------------------------------------------
