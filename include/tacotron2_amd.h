@@ -1128,6 +1128,33 @@ int t2amd_token_average_f32(const float* v, long long vb, long long vt, const fl
 int t2amd_token_average_bwd_f32(const float* g, const float* den, const float* w, long long wb, const int* path, int B, int N_max,
                                 int T, int C, float* dv, void* stream);
 
+/* Masked multi-head self-attention (csrc/self_attn.hip, csrc/self_attn_rows.hip): per utterance b with
+ * T_b = lengths[b] frames (device int32, clamped into [0, T]; NULL: T) and per head h, s(t, j) = scale sum_d q(t, d) k(j, d),
+ * p = softmax over j < T_b, o(t, :) = sum_j p(t, j) v(j, :) for t < T_b and +0 from there on; lse(t) = log sum_j exp s(t, j).
+ * Element (b, t, h, d) of q, k, v and g lies at x[b * xb + t * xt + h * xh + d]: strides that are multiples of 4 floats, bases
+ * aligned to 16 bytes; what lies at and beyond T_b is never read.  o, dq, dk, dv are contiguous (B, T, H, D), lse (B, H, T).
+ * D in {32, 64, 96, 128}, 1 <= H <= 16, T <= 4096, B H <= 65535.  Exact f32, no atomics, one writer per element, every sum in a
+ * fixed ascending order.  Error texts begin with "self_attn:". */
+/* *max_frames = 4096, *max_heads = 16, *min_width = 32, *max_width = 128, *max_batch_heads = 65535. */
+int t2amd_self_attn_limits(int* max_frames, int* max_heads, int* min_width, int* max_width, int* max_batch_heads);
+/* which 0: the forward's workspace (none: 0 bytes); 1: the bytes of the lse the forward writes for a backward; 2: the
+ * backward's workspace (delta, (B, H, T)). */
+int t2amd_self_attn_workspace(int B, int T, int H, int D, int which, long long* bytes);
+/* lse NULL: not kept. */
+int t2amd_self_attn_f32(const float* q, long long qb, long long qt, long long qh, const float* k, long long kb, long long kt,
+                        long long kh, const float* v, long long vb, long long vt, long long vh, const int* lengths, int B, int T,
+                        int H, int D, float scale, float* o, float* lse, void* stream);
+/* delta (B, H, T): delta(t) = sum_d g(t, d) o(t, d) as an fmaf chain per lane over d = lane, lane + 64 and a xor butterfly; +0
+ * at and beyond T_b.  The first launch of the backward, callable alone. */
+int t2amd_self_attn_delta_f32(const float* g, long long gb, long long gt, long long gh, const float* o, const int* lengths, int B,
+                              int T, int H, int D, float* delta, void* stream);
+/* dq, dk, dv from g = dL/do; o and lse are what t2amd_self_attn_f32 wrote on the same operands; ws holds at least
+ * t2amd_self_attn_workspace(.., 2) bytes.  All three gradients are +0 at and beyond T_b. */
+int t2amd_self_attn_bwd_f32(const float* q, long long qb, long long qt, long long qh, const float* k, long long kb, long long kt,
+                            long long kh, const float* v, long long vb, long long vt, long long vh, const float* o, const float* lse,
+                            const float* g, long long gb, long long gt, long long gh, const int* lengths, int B, int T, int H, int D,
+                            float scale, float* dq, float* dk, float* dv, unsigned char* ws, long long ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
  * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are

@@ -299,6 +299,8 @@ SYMBOLS = [
     "t2amd_beta_binomial_log_prior_f32",
     "t2amd_regulate_limits", "t2amd_durations_to_path_i32", "t2amd_length_regulate_f32", "t2amd_length_regulate_bwd_f32",
     "t2amd_token_average_f32", "t2amd_token_average_bwd_f32",
+    "t2amd_self_attn_limits", "t2amd_self_attn_workspace", "t2amd_self_attn_f32", "t2amd_self_attn_delta_f32",
+    "t2amd_self_attn_bwd_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
@@ -444,6 +446,11 @@ def _argtypes():
         "t2amd_length_regulate_bwd_f32": [_P, _L, _L, _P, _I, _I, _I, _I, _P, _P],
         "t2amd_token_average_f32": [_P, _L, _L, _P, _L, _P, _I, _I, _I, _I, _P, _P, _P, _P],
         "t2amd_token_average_bwd_f32": [_P, _P, _P, _L, _P, _I, _I, _I, _I, _P, _P],
+        "t2amd_self_attn_limits": [pt(C.c_int)] * 5,
+        "t2amd_self_attn_workspace": [_I, _I, _I, _I, _I, pt(C.c_longlong)],
+        "t2amd_self_attn_f32": [_P, _L, _L, _L] * 3 + [_P, _I, _I, _I, _I, _F, _P, _P, _P],
+        "t2amd_self_attn_delta_f32": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _I, _P, _P],
+        "t2amd_self_attn_bwd_f32": [_P, _L, _L, _L] * 3 + [_P, _P, _P, _L, _L, _L, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _L, _P],
         "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
         "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
@@ -2222,6 +2229,78 @@ def token_average_backward(grad, den, weights, path, dv):
     _check(load().t2amd_token_average_bwd_f32(ptr(_fullc(grad)), ptr(_fullc(den)), pw, _i64(wb),
                                               _regulate_ints(who, path, (B, T), "path"), B, N, T, C_, ptr(_fullc(dv)), _stream()),
            "t2amd_token_average_bwd_f32")
+
+
+# ---- masked multi-head self-attention and its gradient (csrc/self_attn.hip, csrc/self_attn_rows.hip) -----------------------------
+def self_attn_limits():
+    """-> (frames at most, heads at most, least head width, greatest head width, utterances times heads at most)."""
+    v = [C.c_int(0) for _ in range(5)]
+    _check(load().t2amd_self_attn_limits(*[C.byref(x) for x in v]), "t2amd_self_attn_limits")
+    return tuple(x.value for x in v)
+
+
+def self_attn_workspace(B, T, H, D, which=0):
+    """Bytes for B utterances of at most T frames, H heads of width D: ``which`` 0 the forward's workspace (none), 1 the lse the
+    forward keeps for a backward, 2 the backward's workspace."""
+    n = C.c_longlong(0)
+    _check(load().t2amd_self_attn_workspace(int(B), int(T), int(H), int(D), int(which), C.byref(n)), "t2amd_self_attn_workspace")
+    return n.value
+
+
+def _self_attn_operand(who, x, name, shape=None):
+    """(pointer, batch stride, time stride, head stride) of a (B, T, H, D) float32 tensor with unit stride along D."""
+    if x.dim() != 4 or min(x.shape) < 1 or x.stride(3) != 1 or (shape is not None and tuple(x.shape) != tuple(shape)):
+        raise NativeError("%s: expected %s (B, T, H, D)%s with unit stride along D, got shape %s stride %s"
+                          % (who, name, "" if shape is None else " = %s" % (tuple(shape),), tuple(x.shape), x.stride()))
+    return [ptr(x)] + [_i64(x.stride(i) if x.shape[i] > 1 else 0) for i in range(3)]       # an axis of one element has no stride
+
+
+def _self_attn_rows(who, x, name, B, H, T):
+    if x is not None and (tuple(x.shape) != (B, H, T) or not x.is_contiguous()):
+        raise NativeError("%s: expected contiguous %s (%d, %d, %d), got shape %s stride %s" % (who, name, B, H, T, tuple(x.shape), x.stride()))
+    return ptr(x)
+
+
+def self_attn(q, k, v, lengths, scale, o, lse=None):
+    """o (B, T, H, D) contiguous float32 = softmax(scale q k^T) v per head over each utterance's own ``lengths[b]`` frames (device
+    int32, clamped; None: T), +0 at and beyond them; q, k, v (B, T, H, D) float32 with unit stride along D, the other strides
+    multiples of 4 floats and 16-byte bases; ``lse`` (B, H, T) or None receives the row logsumexp a backward reads."""
+    who = "self_attn"
+    aq = _self_attn_operand(who, q, "q")
+    B, T, H, D = q.shape
+    ak, av = _self_attn_operand(who, k, "k", q.shape), _self_attn_operand(who, v, "v", q.shape)
+    _self_attn_operand(who, o, "o", q.shape)
+    _check(load().t2amd_self_attn_f32(*(aq + ak + av + [_pair_lengths(who, lengths, B), B, T, H, D, float(scale), ptr(_fullc(o)),
+                                                         _self_attn_rows(who, lse, "lse", B, H, T), _stream()])),
+           "t2amd_self_attn_f32")
+
+
+def self_attn_delta(g, o, lengths, delta):
+    """delta (B, H, T) contiguous float32 = sum_d g o per row, +0 at and beyond an utterance's frames: the backward's row pass."""
+    who = "self_attn_delta"
+    ag = _self_attn_operand(who, g, "the gradient")
+    B, T, H, D = g.shape
+    _self_attn_operand(who, o, "o", g.shape)
+    _check(load().t2amd_self_attn_delta_f32(*(ag + [ptr(_fullc(o)), _pair_lengths(who, lengths, B), B, T, H, D,
+                                                     _self_attn_rows(who, delta, "delta", B, H, T), _stream()])),
+           "t2amd_self_attn_delta_f32")
+
+
+def self_attn_backward(q, k, v, o, lse, g, lengths, scale, dq, dk, dv, ws):
+    """dq, dk, dv (B, T, H, D) contiguous float32 from ``g`` = dL/do (strided as q, k, v may be); ``o`` and ``lse`` are those of a
+    ``self_attn`` call on the same operands, ``ws`` a uint8 tensor of at least ``self_attn_workspace(B, T, H, D, 2)`` bytes."""
+    who = "self_attn_backward"
+    aq = _self_attn_operand(who, q, "q")
+    B, T, H, D = q.shape
+    ak, av = _self_attn_operand(who, k, "k", q.shape), _self_attn_operand(who, v, "v", q.shape)
+    ag = _self_attn_operand(who, g, "the gradient", q.shape)
+    for name, t in (("o", o), ("dq", dq), ("dk", dk), ("dv", dv)):
+        _self_attn_operand(who, t, name, q.shape)
+        _fullc(t)
+    pw, nw = _forward_sum_ws(who, ws)
+    _check(load().t2amd_self_attn_bwd_f32(*(aq + ak + av + [ptr(o), _self_attn_rows(who, lse, "lse", B, H, T)] + ag
+                                            + [_pair_lengths(who, lengths, B), B, T, H, D, float(scale), ptr(dq), ptr(dk), ptr(dv),
+                                               pw, nw, _stream()])), "t2amd_self_attn_bwd_f32")
 
 
 # ----------------------------------------------------------------------------
