@@ -1155,6 +1155,46 @@ int t2amd_self_attn_bwd_f32(const float* q, long long qb, long long qt, long lon
                             const float* g, long long gb, long long gt, long long gh, const int* lengths, int B, int T, int H, int D,
                             float scale, float* dq, float* dk, float* dv, unsigned char* ws, long long ws_bytes, void* stream);
 
+/* The feed-forward Transformer block's convolutional feed-forward and add + LayerNorm (csrc/fft_block.hip,
+ * csrc/fft_block_rows.hip) over a ragged batch: utterance b has T_b = lengths[b] frames (device int32,
+ * clamped into [0, T]; NULL: T).  Every tensor is float32, channel-last and contiguous (B, T, C), but a convolution's input x,
+ * whose element (b, t, i) lies at x[b * xb + t * xt + i] (strides that are multiples of 4 floats, a base aligned to 16 bytes).
+ * Each utterance is convolved as if it were alone: frames outside [0, T_b) are absent.  Rows at and beyond T_b are never read and
+ * every output is +0 there.  Channels of a convolution are multiples of 32, at most 4096; k is odd, at most 9; T <= 4096;
+ * B <= 65535; LayerNorm channels are multiples of 4 from 32 to 4096.  Exact f32, no atomics, one writer per element, every sum in
+ * a fixed order.  Error texts begin with "fft_block:". */
+/* *max_frames = 4096, *max_channels = 4096, *max_taps = 9, *min_norm_channels = 32, *max_batch = 65535. */
+int t2amd_fft_block_limits(int* max_frames, int* max_channels, int* max_taps, int* min_norm_channels, int* max_batch);
+/* which 0: t2amd_ffb_conv_f32 (none: 0 bytes); 1: t2amd_ffb_conv_dw_f32 (the transposed gradient slab and the slices' partial
+ * sums); 2: t2amd_ffb_colsum_f32 over Cout channels (the partial sums; Cin and k are not read). */
+int t2amd_fft_block_workspace(int B, int T, int Cin, int Cout, int k, int which, long long* bytes);
+/* y(b, t, o) = act(bias(o) + sum_{j, i} image[o][j Cin + i] x(b, t + j - k/2, i)) for t < T_b, an fmaf chain over j then i
+ * ascending from +0, then the bias.  image is [Cout][k Cin]; bias NULL: none; relu != 0: max(., 0); mask (B, T, Cout) non-NULL:
+ * the value is kept only where mask > 0.  The input gradient is the same call on the image of the flipped, transposed weights. */
+int t2amd_ffb_conv_f32(const float* x, long long xb, long long xt, const float* image, const float* bias, const float* mask,
+                       const int* lengths, int B, int T, int Cin, int Cout, int k, int relu, float* y, void* stream);
+/* dw (Cout, Cin, k) = sum over b, then t ascending of g(b, t, o) x(b, t + j - k/2, i): the reduction index b Tp + t (Tp = T
+ * rounded up to 32) is cut into slices that depend on B and T alone, each an ascending fmaf chain, added in ascending order. */
+int t2amd_ffb_conv_dw_f32(const float* g, const float* x, long long xb, long long xt, const int* lengths, int B, int T, int Cin,
+                          int Cout, int k, float* dw, unsigned char* ws, long long ws_bytes, void* stream);
+/* The two row passes of t2amd_ffb_conv_dw_f32, callable alone: the slab of g (B, T, C) transposed per slice, and the slice sum. */
+int t2amd_ffb_transpose_f32(const float* g, const int* lengths, int B, int T, int C, float* out, long long out_bytes, void* stream);
+int t2amd_ffb_dw_finish_f32(const float* part, int slices, int Cin, int Cout, int k, float* dw, void* stream);
+/* y = LayerNorm(x + residual) weight + bias per row t < T_b (two-pass variance).  residual NULL: none.  weight and bias NULL: y is
+ * x + residual itself ("add and mask"; mean and rstd must then be NULL).  z (B, T, C), mean and rstd (B, T) non-NULL: kept for
+ * the backward (z = x + residual). */
+int t2amd_ffb_add_ln_f32(const float* x, const float* residual, const float* weight, const float* bias, const int* lengths, int B,
+                         int T, int C, float eps, float* y, float* z, float* mean, float* rstd, void* stream);
+/* dz = the LayerNorm input gradient of g, from the kept z, mean and rstd. */
+int t2amd_ffb_add_ln_bwd_f32(const float* g, const float* z, const float* mean, const float* rstd, const float* weight,
+                             const int* lengths, int B, int T, int C, float* dz, void* stream);
+/* dbias(c) = sum of g(b, t, c), dweight(c) = sum of g (z - mean) rstd over the real rows: partial sums over runs of the flattened
+ * (b, t), then their ascending sum.  z NULL: dbias alone (a convolution's). */
+int t2amd_ffb_colsum_f32(const float* g, const float* z, const float* mean, const float* rstd, const int* lengths, int B, int T,
+                         int C, float* dbias, float* dweight, unsigned char* ws, long long ws_bytes, void* stream);
+/* out = g where y > 0 and +0 elsewhere: the gradient below a ReLU. */
+int t2amd_ffb_relu_mask_f32(const float* g, const float* y, const int* lengths, int B, int T, int C, float* out, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
  * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are

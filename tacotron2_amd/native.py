@@ -301,6 +301,8 @@ SYMBOLS = [
     "t2amd_token_average_f32", "t2amd_token_average_bwd_f32",
     "t2amd_self_attn_limits", "t2amd_self_attn_workspace", "t2amd_self_attn_f32", "t2amd_self_attn_delta_f32",
     "t2amd_self_attn_bwd_f32",
+    "t2amd_fft_block_limits", "t2amd_fft_block_workspace", "t2amd_ffb_conv_f32", "t2amd_ffb_conv_dw_f32", "t2amd_ffb_transpose_f32",
+    "t2amd_ffb_dw_finish_f32", "t2amd_ffb_add_ln_f32", "t2amd_ffb_add_ln_bwd_f32", "t2amd_ffb_colsum_f32", "t2amd_ffb_relu_mask_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
@@ -451,6 +453,16 @@ def _argtypes():
         "t2amd_self_attn_f32": [_P, _L, _L, _L] * 3 + [_P, _I, _I, _I, _I, _F, _P, _P, _P],
         "t2amd_self_attn_delta_f32": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _I, _P, _P],
         "t2amd_self_attn_bwd_f32": [_P, _L, _L, _L] * 3 + [_P, _P, _P, _L, _L, _L, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _L, _P],
+        "t2amd_fft_block_limits": [pt(C.c_int)] * 5,
+        "t2amd_fft_block_workspace": [_I, _I, _I, _I, _I, _I, pt(C.c_longlong)],
+        "t2amd_ffb_conv_f32": [_P, _L, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
+        "t2amd_ffb_conv_dw_f32": [_P, _P, _L, _L, _P, _I, _I, _I, _I, _I, _P, _P, _L, _P],
+        "t2amd_ffb_transpose_f32": [_P, _P, _I, _I, _I, _P, _L, _P],
+        "t2amd_ffb_dw_finish_f32": [_P, _I, _I, _I, _I, _P, _P],
+        "t2amd_ffb_add_ln_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P],
+        "t2amd_ffb_add_ln_bwd_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
+        "t2amd_ffb_colsum_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
+        "t2amd_ffb_relu_mask_f32": [_P, _P, _P, _I, _I, _I, _P, _P],
         "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
         "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
@@ -2301,6 +2313,113 @@ def self_attn_backward(q, k, v, o, lse, g, lengths, scale, dq, dk, dv, ws):
     _check(load().t2amd_self_attn_bwd_f32(*(aq + ak + av + [ptr(o), _self_attn_rows(who, lse, "lse", B, H, T)] + ag
                                             + [_pair_lengths(who, lengths, B), B, T, H, D, float(scale), ptr(dq), ptr(dk), ptr(dv),
                                                pw, nw, _stream()])), "t2amd_self_attn_bwd_f32")
+
+
+# ---- the feed-forward Transformer block's convolutional feed-forward and add + LayerNorm (csrc/fft_block.hip, fft_block_rows.hip) ----
+def fft_block_limits():
+    """-> (frames at most, channels at most, kernel width at most, least LayerNorm width, utterances at most)."""
+    v = [C.c_int(0) for _ in range(5)]
+    _check(load().t2amd_fft_block_limits(*[C.byref(x) for x in v]), "t2amd_fft_block_limits")
+    return tuple(x.value for x in v)
+
+
+def fft_block_workspace(B, T, Cin, Cout, k, which):
+    """Bytes for B utterances of at most T frames: ``which`` 0 a convolution (none), 1 its weight gradient (the transposed
+    gradient slab and the slices' partial sums), 2 the column sums over Cout channels."""
+    n = C.c_longlong(0)
+    _check(load().t2amd_fft_block_workspace(int(B), int(T), int(Cin), int(Cout), int(k), int(which), C.byref(n)),
+           "t2amd_fft_block_workspace")
+    return n.value
+
+
+def _ffb_rows(who, x, name, shape):
+    if x is not None and (tuple(x.shape) != tuple(shape) or not x.is_contiguous()):
+        raise NativeError("%s: expected contiguous %s %s, got shape %s stride %s" % (who, name, tuple(shape), tuple(x.shape), x.stride()))
+    return ptr(x)
+
+
+def _ffb_x(who, x):
+    """(pointer, batch stride, frame stride) of a (B, T, C) float32 tensor with unit stride along C."""
+    if x.dim() != 3 or min(x.shape) < 1 or x.stride(2) != 1:
+        raise NativeError("%s: expected x (B, T, C) with unit stride along C, got shape %s stride %s" % (who, tuple(x.shape), x.stride()))
+    return [ptr(x)] + [_i64(x.stride(i) if x.shape[i] > 1 else 0) for i in range(2)]
+
+
+def ffb_conv(x, image, bias, mask, lengths, k, relu, y):
+    """y (B, T, Cout) contiguous = the ragged convolution of x (B, T, Cin) (unit channel stride) under the tap-major weight
+    ``image`` (Cout, k Cin), every utterance alone over its own ``lengths[b]`` frames (device int32, clamped; None: T), +0 at and
+    beyond them; ``bias`` (Cout) or None, ``relu``, and ``mask`` (B, T, Cout) or None: y is kept only where mask > 0."""
+    who = "ffb_conv"
+    ax = _ffb_x(who, x)
+    B, T, Cin = x.shape
+    Cout = y.shape[2] if y.dim() == 3 else -1
+    _check(load().t2amd_ffb_conv_f32(*(ax + [_ffb_rows(who, image, "the weight image", (Cout, k * Cin)), _ffb_rows(who, bias, "bias", (Cout,)),
+                                              _ffb_rows(who, mask, "mask", (B, T, Cout)), _pair_lengths(who, lengths, B), B, T, Cin, Cout,
+                                              int(k), int(bool(relu)), _ffb_rows(who, y, "y", (B, T, Cout)), _stream()])),
+           "t2amd_ffb_conv_f32")
+
+
+def ffb_conv_dw(g, x, lengths, k, dw, ws):
+    """dw (Cout, Cin, k) contiguous = sum over b then t of g(b, t, o) x(b, t + j - k // 2, i); g (B, T, Cout) contiguous, ``ws`` a
+    uint8 tensor of at least ``fft_block_workspace(B, T, Cin, Cout, k, 1)`` bytes."""
+    who = "ffb_conv_dw"
+    ax = _ffb_x(who, x)
+    B, T, Cin = x.shape
+    Cout = g.shape[2] if g.dim() == 3 else -1
+    pw, nw = _forward_sum_ws(who, ws)
+    _check(load().t2amd_ffb_conv_dw_f32(*([_ffb_rows(who, g, "g", (B, T, Cout))] + ax
+                                          + [_pair_lengths(who, lengths, B), B, T, Cin, Cout, int(k),
+                                             _ffb_rows(who, dw, "dw", (Cout, Cin, k)), pw, nw, _stream()])), "t2amd_ffb_conv_dw_f32")
+
+
+def ffb_add_ln(x, residual, weight, bias, lengths, eps, y, z=None, mean=None, rstd=None):
+    """y = LayerNorm(x + residual) weight + bias over the last axis of (B, T, C) on the rows below ``lengths``, +0 beyond;
+    ``weight`` None: y = x + residual ("add and mask").  ``z`` (B, T, C), ``mean`` and ``rstd`` (B, T) are kept where given."""
+    who = "ffb_add_ln"
+    if x.dim() != 3:
+        raise NativeError("%s: expected x (B, T, C), got %s" % (who, tuple(x.shape)))
+    B, T, C_ = x.shape
+    _check(load().t2amd_ffb_add_ln_f32(_ffb_rows(who, x, "x", x.shape), _ffb_rows(who, residual, "residual", x.shape),
+                                       _ffb_rows(who, weight, "weight", (C_,)), _ffb_rows(who, bias, "bias", (C_,)),
+                                       _pair_lengths(who, lengths, B), B, T, C_, float(eps), _ffb_rows(who, y, "y", x.shape),
+                                       _ffb_rows(who, z, "z", x.shape), _ffb_rows(who, mean, "mean", (B, T)),
+                                       _ffb_rows(who, rstd, "rstd", (B, T)), _stream()), "t2amd_ffb_add_ln_f32")
+
+
+def ffb_add_ln_backward(g, z, mean, rstd, weight, lengths, dz):
+    """dz (B, T, C) = the LayerNorm input gradient of g from the kept z, mean and rstd."""
+    who = "ffb_add_ln_backward"
+    if z.dim() != 3:
+        raise NativeError("%s: expected z (B, T, C), got %s" % (who, tuple(z.shape)))
+    B, T, C_ = z.shape
+    _check(load().t2amd_ffb_add_ln_bwd_f32(_ffb_rows(who, g, "g", z.shape), _ffb_rows(who, z, "z", z.shape),
+                                           _ffb_rows(who, mean, "mean", (B, T)), _ffb_rows(who, rstd, "rstd", (B, T)),
+                                           _ffb_rows(who, weight, "weight", (C_,)), _pair_lengths(who, lengths, B), B, T, C_,
+                                           _ffb_rows(who, dz, "dz", z.shape), _stream()), "t2amd_ffb_add_ln_bwd_f32")
+
+
+def ffb_colsum(g, z, mean, rstd, lengths, dbias, dweight, ws):
+    """dbias (C) = the column sums of g (B, T, C) over the real rows and, with z, mean and rstd, dweight (C) = those of
+    g (z - mean) rstd; ``ws`` a uint8 tensor of at least ``fft_block_workspace(B, T, C, C, 1, 2)`` bytes."""
+    who = "ffb_colsum"
+    if g.dim() != 3:
+        raise NativeError("%s: expected g (B, T, C), got %s" % (who, tuple(g.shape)))
+    B, T, C_ = g.shape
+    pw, nw = _forward_sum_ws(who, ws)
+    _check(load().t2amd_ffb_colsum_f32(_ffb_rows(who, g, "g", g.shape), _ffb_rows(who, z, "z", g.shape), _ffb_rows(who, mean, "mean", (B, T)),
+                                       _ffb_rows(who, rstd, "rstd", (B, T)), _pair_lengths(who, lengths, B), B, T, C_,
+                                       _ffb_rows(who, dbias, "dbias", (C_,)), _ffb_rows(who, dweight, "dweight", (C_,)), pw, nw, _stream()),
+           "t2amd_ffb_colsum_f32")
+
+
+def ffb_relu_mask(g, y, lengths, out):
+    """out = g where y > 0 and +0 elsewhere and beyond ``lengths``: the gradient below a ReLU; all (B, T, C) contiguous."""
+    who = "ffb_relu_mask"
+    if g.dim() != 3:
+        raise NativeError("%s: expected g (B, T, C), got %s" % (who, tuple(g.shape)))
+    B, T, C_ = g.shape
+    _check(load().t2amd_ffb_relu_mask_f32(_ffb_rows(who, g, "g", g.shape), _ffb_rows(who, y, "y", g.shape), _pair_lengths(who, lengths, B),
+                                          B, T, C_, _ffb_rows(who, out, "out", g.shape), _stream()), "t2amd_ffb_relu_mask_f32")
 
 
 # ----------------------------------------------------------------------------
