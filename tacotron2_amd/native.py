@@ -1214,16 +1214,19 @@ def _seg(t, width, dtype=torch.float32, x3=False):
 def lstm_step_fwd(xs, widths, W, H, B, gates_out, c_out, h_out, gin=None, bias=None, c_prev=None,
                   keep=None, keep_scale=1.0, lens=None, t=0, small=False, bf16=False, h16_out=None):
     """``bf16=True``: xs and W are torch.bfloat16 (MFMA operands), everything else stays f32.  ``bf16=3``: xs, W and h16_out are
-    split-bf16 images (split_bf16x3: bfloat16 tensors with two columns per k) -- the 'bf16x3' mode of the wide tile."""
+    split-bf16 images (split_bf16x3: bfloat16 tensors with two columns per k) -- the 'bf16x3' mode of the wide tile.
+    ``bf16=2`` (``small=True`` only): W alone is torch.bfloat16, xs stay f32 -- the decode loops' bf16-weight matrix-vector form.
+    ``gates_out=None``: the gates are not written."""
     lib = load()
     a = LstmStep()
     a.nseg = len(xs)
     x3 = bf16 == 3 and bf16 is not True
-    odt = torch.bfloat16 if bf16 else torch.float32
+    w_only = bf16 == 2 and bf16 is not True
+    odt = torch.bfloat16 if bf16 and not w_only else torch.float32
     for i, (x, w) in enumerate(zip(xs, widths)):
         a.x[i] = _seg(x, w, odt, x3)
-    a.W = ptr(_fullc(W), odt)
-    a.bf16 = 3 if x3 else (1 if bf16 else 0)
+    a.W = ptr(_fullc(W), torch.bfloat16 if bf16 else torch.float32)
+    a.bf16 = 3 if x3 else 2 if w_only else (1 if bf16 else 0)
     if h16_out is not None:
         a.h16_out, a.ld_h16 = _mat(h16_out, torch.bfloat16)[:2]
         if x3:
@@ -1234,7 +1237,8 @@ def lstm_step_fwd(xs, widths, W, H, B, gates_out, c_out, h_out, gin=None, bias=N
     a.bias = ptr(bias)
     if c_prev is not None:
         a.c_prev, a.ld_cprev = _mat(c_prev)[:2]
-    a.gates_out, a.ld_gates = _mat(gates_out)[:2]
+    if gates_out is not None:
+        a.gates_out, a.ld_gates = _mat(gates_out)[:2]
     a.c_out, a.ld_c = _mat(c_out)[:2]
     a.h_out, a.ld_h = _mat(h_out)[:2]
     if keep is not None:
