@@ -28,7 +28,9 @@ import numpy as np
 import torch
 
 from . import native as nv
-from .audio import _lengths, _require_device
+from . import ragged as rg
+from .audio import _lengths
+from .ragged import dense_rows as _dense_rows, require_device as _require_device
 
 MAX_FRAMES = 4096
 MAX_TOKENS = 1024
@@ -44,39 +46,15 @@ def monotonic_align(scores, t_lengths=None, n_lengths=None, return_path=False):
     utterance needs 1 <= N <= T, T <= 4096, N <= 1024.  -> ``durations`` (B, N) int32, the frames on each token (zeros at and
     beyond an utterance's N; a row sums to its T), ``score`` (B,) float32 = Q(T-1, N-1), and with ``return_path`` also ``path``
     (B, T) int32, the token of every frame (-1 at and beyond T)."""
-    if not torch.is_tensor(scores) or scores.dtype != torch.float32:
-        raise TypeError("monotonic_align: expected a float32 tensor, got %s"
-                        % (scores.dtype if torch.is_tensor(scores) else type(scores).__name__))
-    if scores.dim() == 2:
-        scores = scores.unsqueeze(0)
-    if scores.dim() != 3 or min(scores.shape) < 1:
-        raise ValueError("monotonic_align: expected (B, T, N) or (T, N) scores, got shape %s" % (tuple(scores.shape),))
-    _require_device(scores)
-    scores = scores.detach()
+    scores, tl, nl = _path_args("monotonic_align", scores, t_lengths, n_lengths)
     B, T, N = scores.shape
-    tl = _lengths(t_lengths, B, None, "monotonic_align: t_", full=T)
-    nl = _lengths(n_lengths, B, None, "monotonic_align: n_", full=N)
-    for b in range(B):
-        if not (1 <= tl[b] <= T and 1 <= nl[b] <= N):
-            raise ValueError("monotonic_align: utterance %d: %d frames and %d tokens do not lie in [1, %d] and [1, %d]"
-                             % (b, tl[b], nl[b], T, N))
-        if tl[b] > MAX_FRAMES or nl[b] > MAX_TOKENS:
-            raise ValueError("monotonic_align: utterance %d: %d frames and %d tokens exceed the limits of %d frames and %d tokens"
-                             % (b, tl[b], nl[b], MAX_FRAMES, MAX_TOKENS))
-        if nl[b] > tl[b]:
-            raise ValueError("monotonic_align: utterance %d has %d tokens and only %d frames; a monotonic path needs 1 <= N <= T"
-                             % (b, nl[b], tl[b]))
-    Tm, Nm = max(tl), max(nl)
+    s, t_dev, n_dev = _longest_part(scores, tl, nl)
+    Tm, Nm = s.shape[1:]
     dev = scores.device
-    s = scores[:, :Tm, :Nm]
-    if Nm > 1 and s.stride(2) != 1:
-        s = s.contiguous()
-    t_dev, n_dev = (torch.tensor(v, dtype=torch.int32).to(dev) for v in (tl, nl))
     durations = torch.empty(B, Nm, dtype=torch.int32, device=dev)
     score = torch.empty(B, dtype=torch.float32, device=dev)
     path = torch.empty(B, Tm, dtype=torch.int32, device=dev) if return_path else None
-    ws = torch.empty(nv.align_workspace(B, Tm, Nm), dtype=torch.uint8, device=dev)
-    nv.monotonic_align(s, t_dev, n_dev, durations, score, path, ws)
+    nv.monotonic_align(s, t_dev, n_dev, durations, score, path, rg.workspace(nv.align_workspace(B, Tm, Nm), dev))
     if Nm < N:                                                              # a longer buffer holding shorter utterances
         durations = torch.nn.functional.pad(durations, (0, N - Nm))
     if return_path and Tm < T:
@@ -122,43 +100,32 @@ def alignment_metrics(alignments, path, input_lengths, output_lengths):
     return out
 
 
-def _forward_sum_args(scores, t_lengths, n_lengths):
-    """The validation of ``monotonic_align`` under the prefix ``forward_sum:`` -> (scores as (B, T, N), frames, tokens)."""
-    if not torch.is_tensor(scores) or scores.dtype != torch.float32:
-        raise TypeError("forward_sum: expected a float32 tensor, got %s"
-                        % (scores.dtype if torch.is_tensor(scores) else type(scores).__name__))
+def _path_args(who, scores, t_lengths, n_lengths):
+    """What ``monotonic_align`` and the forward-sum functions ask of their arguments -> (scores as (B, T, N), frames, tokens)."""
+    rg.float32(who, scores)
     if scores.dim() == 2:
         scores = scores.unsqueeze(0)
     if scores.dim() != 3 or min(scores.shape) < 1:
-        raise ValueError("forward_sum: expected (B, T, N) or (T, N) scores, got shape %s" % (tuple(scores.shape),))
+        raise ValueError("%s: expected (B, T, N) or (T, N) scores, got shape %s" % (who, tuple(scores.shape)))
     _require_device(scores)
     B, T, N = scores.shape
-    tl = _lengths(t_lengths, B, None, "forward_sum: t_", full=T)
-    nl = _lengths(n_lengths, B, None, "forward_sum: n_", full=N)
-    for b in range(B):
-        if not (1 <= tl[b] <= T and 1 <= nl[b] <= N):
-            raise ValueError("forward_sum: utterance %d: %d frames and %d tokens do not lie in [1, %d] and [1, %d]"
-                             % (b, tl[b], nl[b], T, N))
-        if tl[b] > MAX_FRAMES or nl[b] > MAX_TOKENS:
-            raise ValueError("forward_sum: utterance %d: %d frames and %d tokens exceed the limits of %d frames and %d tokens"
-                             % (b, tl[b], nl[b], MAX_FRAMES, MAX_TOKENS))
-        if nl[b] > tl[b]:
-            raise ValueError("forward_sum: utterance %d has %d tokens and only %d frames; a monotonic path needs 1 <= N <= T"
-                             % (b, nl[b], tl[b]))
-    return scores, tl, nl
+    return (scores,) + rg.path_lengths(who, t_lengths, n_lengths, B, T, N, (MAX_FRAMES, MAX_TOKENS), monotonic=True)
+
+
+def _longest_part(scores, tl, nl):
+    """The longest utterance's part of ``scores`` with unit stride along N, and the lengths on its device."""
+    s = scores.detach()[:, :max(tl), :max(nl)]
+    if s.shape[2] > 1 and s.stride(2) != 1:
+        s = s.contiguous()
+    return (s,) + rg.upload(scores.device, tl, nl)
 
 
 def _forward_sum_launch(scores, tl, nl, keep):
     """The alpha launch over the longest utterance's part of ``scores`` -> (that part, device lengths, log_z, workspace)."""
-    B = scores.shape[0]
-    Tm, Nm = max(tl), max(nl)
-    dev = scores.device
-    s = scores.detach()[:, :Tm, :Nm]
-    if Nm > 1 and s.stride(2) != 1:
-        s = s.contiguous()
-    t_dev, n_dev = (torch.tensor(v, dtype=torch.int32).to(dev) for v in (tl, nl))
-    log_z = torch.empty(B, dtype=torch.float32, device=dev)
-    ws = torch.empty(nv.forward_sum_workspace(B, Tm, Nm, keep), dtype=torch.uint8, device=dev)
+    s, t_dev, n_dev = _longest_part(scores, tl, nl)
+    B, Tm, Nm = s.shape
+    log_z = torch.empty(B, dtype=torch.float32, device=s.device)
+    ws = rg.workspace(nv.forward_sum_workspace(B, Tm, Nm, keep), s.device)
     nv.forward_sum(s, t_dev, n_dev, log_z, ws, keep)
     return s, t_dev, n_dev, log_z, ws
 
@@ -195,7 +162,7 @@ def forward_sum(scores, t_lengths=None, n_lengths=None):
     ``monotonic_align``.  A score of -inf marks an impossible cell; an utterance without a possible path gives -inf.
     Differentiable: the gradient with respect to ``scores`` is ``grad_output`` times the posterior occupancy gamma (zeros in the
     padding).  Under ``no_grad``, or where ``scores`` does not require a gradient, nothing is kept for a backward pass."""
-    scores, tl, nl = _forward_sum_args(scores, t_lengths, n_lengths)
+    scores, tl, nl = _path_args("forward_sum", scores, t_lengths, n_lengths)
     return _ForwardSum.apply(scores, tl, nl, torch.is_grad_enabled() and scores.requires_grad)
 
 
@@ -205,7 +172,7 @@ def alignment_posterior(scores, t_lengths=None, n_lengths=None):
     at frame t (d log_z / d scores; a row within an utterance sums to 1, zeros in the padding), ``soft_durations`` (B, N) float32,
     its column sums (the expected frames on each token; a row sums to the utterance's T), and ``log_z`` (B,) as ``forward_sum``
     gives it.  An utterance without a possible path has zeros and -inf."""
-    scores, tl, nl = _forward_sum_args(scores, t_lengths, n_lengths)
+    scores, tl, nl = _path_args("forward_sum", scores, t_lengths, n_lengths)
     s, t_dev, n_dev, log_z, ws = _forward_sum_launch(scores, tl, nl, True)
     soft = torch.empty(s.shape[0], s.shape[2], dtype=torch.float32, device=s.device)
     gamma = _forward_sum_gamma(scores.shape, s, t_dev, n_dev, log_z, None, ws, soft)
@@ -225,7 +192,7 @@ class ForwardSumLoss(torch.nn.Module):
         self.reduction, self.per_frame = reduction, bool(per_frame)
 
     def forward(self, scores, t_lengths=None, n_lengths=None):
-        scores, tl, nl = _forward_sum_args(scores, t_lengths, n_lengths)
+        scores, tl, nl = _path_args("forward_sum", scores, t_lengths, n_lengths)
         loss = -forward_sum(scores, tl, nl)
         if self.per_frame:
             loss = loss / torch.tensor(tl, dtype=torch.float32).to(loss.device)
@@ -233,23 +200,7 @@ class ForwardSumLoss(torch.nn.Module):
 
 
 def _aligner_lengths(who, t_lengths, n_lengths, B, T, N):
-    tl = _lengths(t_lengths, B, None, who + ": t_", full=T)
-    nl = _lengths(n_lengths, B, None, who + ": n_", full=N)
-    for b in range(B):
-        if not (1 <= tl[b] <= T and 1 <= nl[b] <= N):
-            raise ValueError("%s: utterance %d: %d frames and %d tokens do not lie in [1, %d] and [1, %d]"
-                             % (who, b, tl[b], nl[b], T, N))
-    if T > MAX_FRAMES or N > MAX_TOKENS:
-        raise ValueError("%s: %d frames and %d tokens exceed the limits of %d frames and %d tokens" % (who, T, N, MAX_FRAMES, MAX_TOKENS))
-    return tl, nl
-
-
-def _dense_rows(x):
-    """``x`` (B, T, N) as the kernels take it: unit stride along N and row and batch strides that cover the matrix (an expanded
-    or transposed tensor is copied)."""
-    B, T, N = x.shape
-    ok = x.stride(2) == 1 and (T == 1 or x.stride(1) >= N) and (B == 1 or x.stride(0) >= (T - 1) * max(x.stride(1), N) + N)
-    return x if ok else x.contiguous()
+    return rg.path_lengths(who, t_lengths, n_lengths, B, T, N, (MAX_FRAMES, MAX_TOKENS))
 
 
 class _AlignerScores(torch.autograd.Function):
@@ -260,9 +211,9 @@ class _AlignerScores(torch.autograd.Function):
         dev = q.device
         qd, kd = q.detach().contiguous(), k.detach().contiguous()
         lp = None if logp is None else _dense_rows(logp.detach())
-        t_dev, n_dev = (torch.tensor(v, dtype=torch.int32).to(dev) for v in (tl, nl))
+        t_dev, n_dev = rg.upload(dev, tl, nl)
         scores = torch.empty(B, T, N, dtype=torch.float32, device=dev)
-        ws = torch.empty(nv.aligner_workspace(B, T, N, C, 1 if keep else 0), dtype=torch.uint8, device=dev)
+        ws = rg.workspace(nv.aligner_workspace(B, T, N, C, 1 if keep else 0), dev)
         nv.aligner_scores(qd, kd, t_dev, n_dev, tau, lp, scores, ws, keep)
         if keep:
             ctx.tau = tau
@@ -278,7 +229,7 @@ class _AlignerScores(torch.autograd.Function):
         g = _dense_rows(grad.float())
         dq, dk = torch.empty_like(q), torch.empty_like(k)
         dlogp = torch.empty(B, T, N, dtype=torch.float32, device=q.device) if ctx.needs_input_grad[2] else None
-        ws = torch.empty(nv.aligner_workspace(B, T, N, C, 2), dtype=torch.uint8, device=q.device)
+        ws = rg.workspace(nv.aligner_workspace(B, T, N, C, 2), q.device)
         nv.aligner_scores_backward(q, k, t_dev, n_dev, ctx.tau, g, dq, dk, dlogp, kept, ws)
         return dq, dk, dlogp, None, None, None, None
 
@@ -293,8 +244,7 @@ def aligner_scores(queries, keys, t_lengths=None, n_lengths=None, temperature=0.
     or where no input requires a gradient, nothing is kept."""
     who = "aligner_scores"
     for name, t in (("queries", queries), ("keys", keys)) + ((("log_prior", log_prior),) if log_prior is not None else ()):
-        if not torch.is_tensor(t) or t.dtype != torch.float32:
-            raise TypeError("%s: expected float32 %s, got %s" % (who, name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+        rg.float32(who, t, name)
     if queries.dim() == 2 and keys.dim() == 2:
         queries, keys = queries.unsqueeze(0), keys.unsqueeze(0)
         if log_prior is not None and log_prior.dim() == 2:
@@ -309,8 +259,7 @@ def aligner_scores(queries, keys, t_lengths=None, n_lengths=None, temperature=0.
         raise ValueError("%s: %d channels exceed the limit of %d" % (who, C, MAX_CHANNELS))
     if log_prior is not None and tuple(log_prior.shape) != (B, T, N):
         raise ValueError("%s: expected a log_prior of shape (%d, %d, %d), got %s" % (who, B, T, N, tuple(log_prior.shape)))
-    if not (isinstance(temperature, (int, float)) and 0.0 < float(temperature) < float("inf")):
-        raise ValueError("%s: the temperature must be a positive number, got %r" % (who, temperature))
+    tau = rg.positive(who, temperature, "the temperature must be a positive number")
     tl, nl = _aligner_lengths(who, t_lengths, n_lengths, B, T, N)
     for name, t in (("queries", queries), ("keys", keys), ("log_prior", log_prior)):
         if t is not None:
@@ -318,7 +267,7 @@ def aligner_scores(queries, keys, t_lengths=None, n_lengths=None, temperature=0.
             if t.device != queries.device:
                 raise ValueError("%s: queries are on %s and %s on %s" % (who, queries.device, name, t.device))
     keep = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (queries, keys, log_prior))
-    return _AlignerScores.apply(queries, keys, log_prior, tl, nl, float(temperature), keep)
+    return _AlignerScores.apply(queries, keys, log_prior, tl, nl, tau, keep)
 
 
 @torch.no_grad()
@@ -334,13 +283,11 @@ def beta_binomial_log_prior(t_lengths, n_lengths, scaling=1.0, T=None, N=None, d
         raise ValueError("%s: expected the frames and tokens of at least one utterance" % who)
     T, N = (max(tl) if T is None else int(T)), (max(nl) if N is None else int(N))
     tl, nl = _aligner_lengths(who, tl, nl, len(tl), T, N)
-    if not (isinstance(scaling, (int, float)) and 0.0 < float(scaling) <= 1e6):
-        raise ValueError("%s: the scaling must lie in (0, 1e6], got %r" % (who, scaling))
+    scaling = rg.positive(who, scaling, "the scaling must lie in (0, 1e6]", cap=1e6)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None and not nv.validate_only() else torch.device(device or "cpu")
     out = torch.empty(len(tl), T, N, dtype=torch.float32, device=dev)
     _require_device(out)
-    t_dev, n_dev = (torch.tensor(v, dtype=torch.int32).to(dev) for v in (tl, nl))
-    nv.beta_binomial_log_prior(t_dev, n_dev, float(scaling), out)
+    nv.beta_binomial_log_prior(*rg.upload(dev, tl, nl), scaling, out)
     return out
 
 
@@ -350,11 +297,10 @@ class AlignerScores(torch.nn.Module):
 
     def __init__(self, temperature=0.0005, prior_scaling=None):
         super().__init__()
-        if not (isinstance(temperature, (int, float)) and 0.0 < float(temperature) < float("inf")):
-            raise ValueError("AlignerScores: the temperature must be a positive number, got %r" % (temperature,))
-        if prior_scaling is not None and not (isinstance(prior_scaling, (int, float)) and 0.0 < float(prior_scaling) <= 1e6):
-            raise ValueError("AlignerScores: prior_scaling must be None or lie in (0, 1e6], got %r" % (prior_scaling,))
-        self.temperature, self.prior_scaling = float(temperature), prior_scaling
+        self.temperature = rg.positive("AlignerScores", temperature, "the temperature must be a positive number")
+        if prior_scaling is not None:
+            rg.positive("AlignerScores", prior_scaling, "prior_scaling must be None or lie in (0, 1e6]", cap=1e6)
+        self.prior_scaling = prior_scaling
 
     def forward(self, queries, keys, t_lengths=None, n_lengths=None):
         prior = None
@@ -388,20 +334,7 @@ def _regulate_args(who, durations, n_lengths, batch_of_one):
     durations = durations.detach()
     if N > 1 and durations.stride(1) != 1 or (B > 1 and durations.stride(0) < N):
         durations = durations.contiguous()
-    dev = durations.device
-    if n_lengths is None:
-        return durations, None
-    if torch.is_tensor(n_lengths) and n_lengths.device.type != "cpu":
-        if n_lengths.device != dev:
-            raise ValueError("%s: durations are on %s and n_lengths on %s" % (who, dev, n_lengths.device))
-        if n_lengths.dim() != 1 or n_lengths.numel() != B:
-            raise ValueError("%s: n_%d lengths for a batch of %d" % (who, n_lengths.numel(), B))
-        return durations, n_lengths.detach().to(torch.int32).contiguous()
-    nl = _lengths(n_lengths, B, None, who + ": n_")
-    for b in range(B):
-        if not 0 <= nl[b] <= N:
-            raise ValueError("%s: utterance %d: %d tokens do not lie in [0, %d]" % (who, b, nl[b], N))
-    return durations, torch.tensor(nl, dtype=torch.int32).to(dev)
+    return durations, rg.device_lengths(who, n_lengths, B, N, durations.device, "durations are", rg.TOKENS)
 
 
 def _regulate_frames(who, durations, n_dev, T):
@@ -451,12 +384,6 @@ def durations_to_path(durations, n_lengths=None, T=None):
     return path, t_lengths
 
 
-def _regulate_grad(g):
-    """A gradient as the kernels take it: float32, unit stride along C, strides that cover the tensor (the expanded gradient of
-    ``.sum().backward()`` is copied)."""
-    return _dense_rows(g.float())
-
-
 class _LengthRegulate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, durations, n_dev, T, keep):
@@ -478,7 +405,7 @@ class _LengthRegulate(torch.autograd.Function):
         if T == 0:
             return torch.zeros(B, ends.shape[1], C, dtype=torch.float32, device=grad.device), None, None, None, None
         dx = torch.empty(B, ends.shape[1], C, dtype=torch.float32, device=grad.device)
-        nv.length_regulate_backward(_regulate_grad(grad), ends, dx)
+        nv.length_regulate_backward(_dense_rows(grad.float()), ends, dx)   # an expanded gradient is copied
         return dx, None, None, None, None
 
 
@@ -495,8 +422,7 @@ def length_regulate(x, durations, n_lengths=None, T=None):
     synchronisation anywhere in the call; an utterance with a negative duration then has ``t_lengths`` = -1 and a ``y`` of
     zeros.  A non-contiguous ``x`` or gradient is made contiguous."""
     who = "length_regulate"
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise TypeError("%s: expected a float32 tensor, got %s" % (who, x.dtype if torch.is_tensor(x) else type(x).__name__))
+    rg.float32(who, x)
     if x.dim() == 2 and torch.is_tensor(durations) and durations.dim() == 1:
         x, durations = x.unsqueeze(0), durations.unsqueeze(0)
     if x.dim() != 3 or min(x.shape) < 1:
@@ -520,11 +446,10 @@ class LengthRegulator(torch.nn.Module):
 
     def __init__(self, pace=1.0, rounding=True, max_len=None):
         super().__init__()
-        if not (isinstance(pace, (int, float)) and 0.0 < float(pace) < float("inf")):
-            raise ValueError("LengthRegulator: the pace must be a positive number, got %r" % (pace,))
+        pace = rg.positive("LengthRegulator", pace, "the pace must be a positive number")
         if max_len is not None and (isinstance(max_len, bool) or not isinstance(max_len, int) or not 0 <= max_len <= MAX_REGULATED_FRAMES):
             raise ValueError("LengthRegulator: max_len must be None or an int in [0, %d], got %r" % (MAX_REGULATED_FRAMES, max_len))
-        self.pace, self.rounding, self.max_len = float(pace), bool(rounding), max_len
+        self.pace, self.rounding, self.max_len = pace, bool(rounding), max_len
 
     def forward(self, x, durations, n_lengths=None):
         if torch.is_tensor(durations) and durations.is_floating_point():
@@ -567,8 +492,7 @@ def token_average(values, durations, n_lengths=None, weights=None):
     utterance's frames; ``weights`` gets no gradient.  The call never synchronises: an utterance with a negative duration is not
     refused, it gives zeros."""
     who = "token_average"
-    if not torch.is_tensor(values) or values.dtype != torch.float32:
-        raise TypeError("%s: expected float32 values, got %s" % (who, values.dtype if torch.is_tensor(values) else type(values).__name__))
+    rg.float32(who, values, "values")
     if values.dim() not in (2, 3) or min(values.shape) < 1:
         raise ValueError("%s: expected (B, T) or (B, T, C) values, got shape %s" % (who, tuple(values.shape)))
     flat = values.dim() == 2
@@ -585,9 +509,7 @@ def token_average(values, durations, n_lengths=None, weights=None):
         raise ValueError("%s: expected durations (%d, N), got shape %s" % (who, B, tuple(d.shape)))
     w = None
     if weights is not None:
-        if not torch.is_tensor(weights) or weights.dtype != torch.float32:
-            raise TypeError("%s: expected float32 weights, got %s"
-                            % (who, weights.dtype if torch.is_tensor(weights) else type(weights).__name__))
+        rg.float32(who, weights, "weights")
         if tuple(weights.shape) != (B, T):
             raise ValueError("%s: expected weights of shape (%d, %d), got %s" % (who, B, T, tuple(weights.shape)))
         if weights.device != v.device:

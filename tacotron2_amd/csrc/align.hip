@@ -170,8 +170,7 @@ __global__ void __launch_bounds__(ALIGN_W) align_kernel(const float* __restrict_
     }
 }
 
-static long long align_ldw(int N_max) { return ((long long)N_max + 3) / 4 * 4; }
-static long long align_slab_bytes(int B, int T_max, int N_max) { return ((long long)B * T_max * align_ldw(N_max) + 7) / 8 * 8; }
+static long long align_slab_bytes(int B, int T_max, int N_max) { return t2_round_up((long long)B * T_max * t2_round_up(N_max, 4), 8); }
 
 static int align_check(int B, int T_max, int N_max, char* msg) {
     const char* what = !(B >= 1 && B <= 1048576)        ? "1 to 2^20 utterances"
@@ -206,16 +205,16 @@ extern "C" int t2amd_monotonic_align_f32(const float* scores, long long sb, long
     char msg[160];
     T2_REQUIRE(scores && t_len && n_len && durations && score && ws, "monotonic_align: null operand");
     if (align_check(B, T_max, N_max, msg) != T2AMD_OK) T2_FAIL(msg);
-    T2_REQUIRE(st >= N_max && (B == 1 || sb >= (T_max - 1) * st + N_max), "monotonic_align: score strides shorter than the matrix");
+    T2_REQUIRE(t2_strides_cover(sb, st, B, T_max, N_max), "monotonic_align: score strides shorter than the matrix");
     const long long slab = align_slab_bytes(B, T_max, N_max);
     T2_REQUIRE(ws_bytes >= slab + 16LL * B, "monotonic_align: the workspace is smaller than t2amd_align_workspace asks for");
     T2_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0, "monotonic_align: the workspace is not aligned to 8 bytes");
-    const long long sbytes = 4 * ((B - 1) * sb + (T_max - 1) * st + N_max);
+    const long long sbytes = t2_span_bytes(sb, st, B, T_max, N_max);
     T2_REQUIRE(!t2_overlap(ws, ws_bytes, scores, sbytes) && !t2_overlap(durations, 4LL * B * N_max, scores, sbytes) &&
                    !t2_overlap(score, 4LL * B, scores, sbytes) && !(path && t2_overlap(path, 4LL * B * T_max, scores, sbytes)),
                "monotonic_align: outputs and workspace must not overlap the scores");
     unsigned long long* stamps = reinterpret_cast<unsigned long long*>(ws + slab);
-    const int ldw = (int)align_ldw(N_max);
+    const int ldw = (int)t2_round_up(N_max, 4);
     if (N_max <= ALIGN_W)
         T2_LAUNCH(align_kernel<1>, dim3((unsigned)B), dim3(ALIGN_W), 0, (hipStream_t)stream, scores, sb, st, t_len, n_len, T_max,
                   N_max, durations, score, path, ws, ldw, stamps);

@@ -17,8 +17,6 @@
 #define AL_MAX_B 65535                  /* utterances: grid.z of the products */
 #define AL_ROWS 16                      /* rows of a workgroup of the row passes: 4 waves, 4 rows each */
 
-static inline long long al_r32(long long n) { return (n + 31) / 32 * 32; }
-static inline long long al_r4(long long n) { return (n + 3) / 4 * 4; }
 
 struct AlFwdWs {
     long long kp, kn, lse, bytes;       // byte offsets
@@ -31,23 +29,23 @@ struct AlBwdWs {
 
 static inline AlFwdWs al_fwd_ws(int B, int T_max, int N_max, int C, int keep) {
     AlFwdWs w;
-    w.Cp = (int)al_r32(C);
+    w.Cp = (int)t2_round_up(C, 32);
     w.kp = 0;
     w.kn = w.kp + 4LL * B * N_max * w.Cp;
-    w.lse = w.kn + 4 * al_r4((long long)B * N_max);
-    w.bytes = w.lse + (keep ? 4 * al_r4((long long)B * T_max) : 0);
+    w.lse = w.kn + 4 * t2_round_up((long long)B * N_max, 4);
+    w.bytes = w.lse + (keep ? 4 * t2_round_up((long long)B * T_max, 4) : 0);
     return w;
 }
 
 static inline AlBwdWs al_bwd_ws(int B, int T_max, int N_max, int C) {
     AlBwdWs w;
-    w.Np = (int)al_r32(N_max);
-    w.Tp = (int)al_r32(T_max);
+    w.Np = (int)t2_round_up(N_max, 32);
+    w.Tp = (int)t2_round_up(T_max, 32);
     w.dz = 0;
     w.kt = w.dz + 4LL * B * T_max * w.Np;
     w.qt = w.kt + 4LL * B * C * w.Np;
     w.cs = w.qt + 4LL * B * C * w.Tp;
-    w.bytes = w.cs + 4 * al_r4((long long)B * N_max);
+    w.bytes = w.cs + 4 * t2_round_up((long long)B * N_max, 4);
     return w;
 }
 

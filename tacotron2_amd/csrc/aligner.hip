@@ -169,8 +169,8 @@ extern "C" int t2amd_aligner_scores_f32(const float* q, const float* k, const in
     const AlFwdWs w = al_fwd_ws(B, T_max, N_max, C, keep);
     T2_PROPAGATE(al_common("aligner_scores", q, k, t_len, n_len, B, T_max, N_max, C, tau, ws, ws_bytes, w.bytes));
     T2_REQUIRE(scores, "aligner_scores: null operand");
-    T2_REQUIRE(st >= N_max && (B == 1 || sb >= (long long)(T_max - 1) * st + N_max), "aligner_scores: score strides shorter than the matrix");
-    const long long sbytes = 4 * ((B - 1) * sb + (T_max - 1) * st + N_max);
+    T2_REQUIRE(t2_strides_cover(sb, st, B, T_max, N_max), "aligner_scores: score strides shorter than the matrix");
+    const long long sbytes = t2_span_bytes(sb, st, B, T_max, N_max);
     T2_REQUIRE(!t2_overlap(scores, sbytes, q, 4LL * B * T_max * C) && !t2_overlap(scores, sbytes, k, 4LL * B * N_max * C) &&
                    !t2_overlap(scores, sbytes, ws, ws_bytes),
                "aligner_scores: the scores must not overlap the inputs or the workspace");

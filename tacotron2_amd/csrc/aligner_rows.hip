@@ -157,9 +157,6 @@ __global__ void __launch_bounds__(256) aligner_prior_kernel(const int* __restric
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-static inline bool al_strides_ok(long long sb, long long st, int B, int T_max, int N_max) {
-    return st >= N_max && (B == 1 || sb >= (long long)(T_max - 1) * st + N_max);
-}
 
 extern "C" int t2amd_aligner_workspace(int B, int T_max, int N_max, int C, int which, long long* bytes) {
     T2_REQUIRE(bytes, "aligner_workspace: null operand");
@@ -175,7 +172,7 @@ extern "C" int t2amd_aligner_pack_keys_f32(const float* k, const int* n_len, int
     T2_PROPAGATE(al_check("aligner_pack_keys", B, 1, N_max, C));
     T2_REQUIRE(t2_aligned16(Kp), "aligner_pack_keys: the key slab is not aligned to 16 bytes");
     T2_LAUNCH(aligner_pack_keys_kernel, dim3((unsigned)t2_cdiv(N_max, 64), (unsigned)B), dim3(256), 0, (hipStream_t)stream, k, n_len,
-              N_max, C, (int)al_r32(C), Kp, kn);
+              N_max, C, (int)t2_round_up(C, 32), Kp, kn);
     T2_LAUNCH_CHECK();
     return T2AMD_OK;
 }
@@ -184,7 +181,7 @@ extern "C" int t2amd_aligner_transpose_f32(const float* x, const int* lens, int 
     T2_REQUIRE(x && lens && out, "aligner_transpose: null operand");
     T2_PROPAGATE(al_check("aligner_transpose", B, R_max, 1, C));
     T2_REQUIRE(t2_aligned16(out), "aligner_transpose: the slab is not aligned to 16 bytes");
-    const int Rp = (int)al_r32(R_max);
+    const int Rp = (int)t2_round_up(R_max, 32);
     T2_LAUNCH(aligner_transpose_kernel, dim3((unsigned)t2_cdiv(Rp, 256), (unsigned)C, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
               x, lens, R_max, C, Rp, out);
     T2_LAUNCH_CHECK();
@@ -195,9 +192,9 @@ extern "C" int t2amd_aligner_rows_fwd_f32(float* scores, long long sb, long long
                                           const int* t_len, const int* n_len, int B, int T_max, int N_max, float* lse, void* stream) {
     T2_REQUIRE(scores && t_len && n_len, "aligner_rows_fwd: null operand");
     T2_PROPAGATE(al_check("aligner_rows_fwd", B, T_max, N_max, 1));
-    T2_REQUIRE(al_strides_ok(sb, st, B, T_max, N_max), "aligner_rows_fwd: score strides shorter than the matrix");
-    T2_REQUIRE(!logp || al_strides_ok(pb, pt, B, T_max, N_max), "aligner_rows_fwd: prior strides shorter than the matrix");
-    const long long sbytes = 4 * ((B - 1) * sb + (T_max - 1) * st + N_max), pbytes = 4 * ((B - 1) * pb + (T_max - 1) * pt + N_max);
+    T2_REQUIRE(t2_strides_cover(sb, st, B, T_max, N_max), "aligner_rows_fwd: score strides shorter than the matrix");
+    T2_REQUIRE(!logp || t2_strides_cover(pb, pt, B, T_max, N_max), "aligner_rows_fwd: prior strides shorter than the matrix");
+    const long long sbytes = t2_span_bytes(sb, st, B, T_max, N_max), pbytes = t2_span_bytes(pb, pt, B, T_max, N_max);
     T2_REQUIRE(!(logp && t2_overlap(scores, sbytes, logp, pbytes)) && !(lse && t2_overlap(scores, sbytes, lse, 4LL * B * T_max)),
                "aligner_rows_fwd: the scores must not overlap the prior or the kept lse");
     T2_LAUNCH(aligner_rows_fwd_kernel, dim3((unsigned)t2_cdiv(T_max, AL_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, scores,
@@ -211,10 +208,10 @@ extern "C" int t2amd_aligner_rows_bwd_f32(const float* g, long long gb, long lon
                                           long long db, long long dt, void* stream) {
     T2_REQUIRE(g && t_len && n_len && lse && dz && colsum, "aligner_rows_bwd: null operand");
     T2_PROPAGATE(al_check("aligner_rows_bwd", B, T_max, N_max, 1));
-    T2_REQUIRE(al_strides_ok(gb, gt, B, T_max, N_max), "aligner_rows_bwd: gradient strides shorter than the matrix");
-    T2_REQUIRE(!dlogp || al_strides_ok(db, dt, B, T_max, N_max), "aligner_rows_bwd: prior gradient strides shorter than the matrix");
-    const int Np = (int)al_r32(N_max);
-    const long long gbytes = 4 * ((B - 1) * gb + (T_max - 1) * gt + N_max), dbytes = 4 * ((B - 1) * db + (T_max - 1) * dt + N_max);
+    T2_REQUIRE(t2_strides_cover(gb, gt, B, T_max, N_max), "aligner_rows_bwd: gradient strides shorter than the matrix");
+    T2_REQUIRE(!dlogp || t2_strides_cover(db, dt, B, T_max, N_max), "aligner_rows_bwd: prior gradient strides shorter than the matrix");
+    const int Np = (int)t2_round_up(N_max, 32);
+    const long long gbytes = t2_span_bytes(gb, gt, B, T_max, N_max), dbytes = t2_span_bytes(db, dt, B, T_max, N_max);
     const long long zbytes = 4LL * B * T_max * Np;
     T2_REQUIRE(!t2_overlap(dz, zbytes, g, gbytes) && !t2_overlap(dz, zbytes, lse, 4LL * B * T_max) &&
                    !t2_overlap(colsum, 4LL * B * N_max, dz, zbytes) && !t2_overlap(colsum, 4LL * B * N_max, g, gbytes) &&

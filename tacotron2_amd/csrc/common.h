@@ -195,6 +195,17 @@ int t2amd_check_lstm_bwd_(const t2amd_lstm_bwd* a);      // rnn.hip: argument ch
 
 static inline bool t2_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int t2_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+static inline long long t2_round_up(long long n, long long m) { return (n + m - 1) / m * m; }
+
+// A padded batch of B matrices of `rows` rows of `cols` floats, batch stride bs and row stride ld (in floats): do the strides
+// cover the matrix, and the bytes from its first float to its last.  The checks of the alignment, aligner, regulator,
+// self-attention and FFT-block entries.
+static inline bool t2_strides_cover(long long bs, long long ld, int B, int rows, long long cols) {
+    return ld >= cols && (B == 1 || bs >= (long long)(rows - 1) * ld + cols);
+}
+static inline long long t2_span_bytes(long long bs, long long ld, int B, int rows, long long cols) {
+    return 4 * ((B - 1) * bs + (long long)(rows - 1) * ld + cols);
+}
 
 // index into y[0..T) of padded sample i (i already shifted by -pad): torch 'reflect' (edge sample not repeated).  The one
 // statement of the mirror rule: the forward pad (audio.hip) and the gradient's fold (audio_bwd.hip) both call it.

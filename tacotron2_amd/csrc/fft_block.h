@@ -21,18 +21,17 @@
 #define FFB_DW_MAX_SLICES 8
 #define FFB_SUM_MAX_PARTS 64
 
-static inline long long ffb_r32(long long n) { return (n + 31) / 32 * 32; }
 
 struct FfbDwPlan {
     int Tp, S, L;                       // frames an utterance takes in the reduction; slices; indices a slice
 };
 static inline FfbDwPlan ffb_dw_plan(int B, int T) {
     FfbDwPlan p;
-    p.Tp = (int)ffb_r32(T);
+    p.Tp = (int)t2_round_up(T, 32);
     const long long K = (long long)B * p.Tp;
     long long S = (K + FFB_DW_SLICE - 1) / FFB_DW_SLICE;
     p.S = (int)(S > FFB_DW_MAX_SLICES ? FFB_DW_MAX_SLICES : S);
-    p.L = (int)ffb_r32((K + p.S - 1) / p.S);
+    p.L = (int)t2_round_up((K + p.S - 1) / p.S, 32);
     return p;
 }
 
@@ -103,4 +102,3 @@ static inline int ffb_check_x(const char* who, const float* x, long long xb, lon
     snprintf(msg, sizeof(msg), "fft_block: %s: %s", who, what);
     T2_FAIL(msg);
 }
-static inline long long ffb_x_span(long long xb, long long xt, int B, int T, int C) { return 4 * ((B - 1) * xb + (T - 1) * xt + C); }

@@ -143,7 +143,7 @@ extern "C" int t2amd_ffb_conv_f32(const float* x, long long xb, long long xt, co
     T2_REQUIRE(image && y, "fft_block: conv: null operand");
     T2_REQUIRE(t2_aligned16(image) && t2_aligned16(y), "fft_block: conv: the weight image and y must be aligned to 16 bytes");
     const long long ybytes = 4LL * B * T * Cout;
-    T2_REQUIRE(!t2_overlap(y, ybytes, x, ffb_x_span(xb, xt, B, T, Cin)) && !t2_overlap(y, ybytes, image, 4LL * Cout * k * Cin) &&
+    T2_REQUIRE(!t2_overlap(y, ybytes, x, t2_span_bytes(xb, xt, B, T, Cin)) && !t2_overlap(y, ybytes, image, 4LL * Cout * k * Cin) &&
                    !(bias && t2_overlap(y, ybytes, bias, 4LL * Cout)) && !(mask && t2_overlap(y, ybytes, mask, ybytes)),
                "fft_block: conv: y must not overlap the inputs");
     FfbConv p = {};
@@ -164,7 +164,7 @@ extern "C" int t2amd_ffb_conv_dw_f32(const float* g, const float* x, long long x
     const FfbDwWs w = ffb_dw_ws(B, T, Cin, Cout, k);
     T2_REQUIRE(ws_bytes >= w.bytes, "fft_block: conv_dw: the workspace is smaller than t2amd_fft_block_workspace asks for");
     T2_REQUIRE(t2_aligned16(ws) && t2_aligned16(g), "fft_block: conv_dw: the workspace and g must be aligned to 16 bytes");
-    const long long gbytes = 4LL * B * T * Cout, wbytes = 4LL * Cout * Cin * k, xbytes = ffb_x_span(xb, xt, B, T, Cin);
+    const long long gbytes = 4LL * B * T * Cout, wbytes = 4LL * Cout * Cin * k, xbytes = t2_span_bytes(xb, xt, B, T, Cin);
     T2_REQUIRE(!t2_overlap(ws, ws_bytes, g, gbytes) && !t2_overlap(ws, ws_bytes, x, xbytes) && !t2_overlap(dw, wbytes, ws, ws_bytes) &&
                    !t2_overlap(dw, wbytes, g, gbytes) && !t2_overlap(dw, wbytes, x, xbytes),
                "fft_block: conv_dw: dw and the workspace must not overlap the inputs or each other");

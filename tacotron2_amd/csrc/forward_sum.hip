@@ -57,8 +57,7 @@ __device__ __forceinline__ float fs_block_max(const float* red, float* red2, int
     return m == fs_ninf() ? 0.0f : m;
 }
 
-static long long fs_ld(int N_max) { return ((long long)N_max + 3) / 4 * 4; }
-static long long fs_slab_bytes(int B, int T_max, int N_max) { return 4LL * B * T_max * fs_ld(N_max); }
+static long long fs_slab_bytes(int B, int T_max, int N_max) { return 4LL * B * T_max * t2_round_up(N_max, 4); }
 
 template <int C>
 __global__ void __launch_bounds__(FS_W) forward_sum_alpha_kernel(const float* __restrict__ scores, long long sb, long long st,
@@ -290,17 +289,17 @@ extern "C" int t2amd_forward_sum_f32(const float* scores, long long sb, long lon
     char msg[160];
     T2_REQUIRE(scores && t_len && n_len && log_z && ws, "forward_sum: null operand");
     if (fs_check(B, T_max, N_max, msg) != T2AMD_OK) T2_FAIL(msg);
-    T2_REQUIRE(st >= N_max && (B == 1 || sb >= (T_max - 1) * st + N_max), "forward_sum: score strides shorter than the matrix");
+    T2_REQUIRE(t2_strides_cover(sb, st, B, T_max, N_max), "forward_sum: score strides shorter than the matrix");
     const long long kept = keep ? fs_kept_bytes(B, T_max, N_max) : 0;
     T2_REQUIRE(ws_bytes >= kept + 16LL * B, "forward_sum: the workspace is smaller than t2amd_forward_sum_workspace asks for");
     T2_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15u) == 0, "forward_sum: the workspace is not aligned to 16 bytes");
-    const long long sbytes = 4 * ((B - 1) * sb + (T_max - 1) * st + N_max);
+    const long long sbytes = t2_span_bytes(sb, st, B, T_max, N_max);
     T2_REQUIRE(!t2_overlap(ws, ws_bytes, scores, sbytes) && !t2_overlap(log_z, 4LL * B, scores, sbytes),
                "forward_sum: outputs and workspace must not overlap the scores");
     float* slab = keep ? reinterpret_cast<float*>(ws) : nullptr;
     double* offs = keep ? reinterpret_cast<double*>(ws + fs_slab_bytes(B, T_max, N_max)) : nullptr;
     unsigned long long* stamps = reinterpret_cast<unsigned long long*>(ws + kept);
-    const int ld = (int)fs_ld(N_max);
+    const int ld = (int)t2_round_up(N_max, 4);
     if (N_max <= FS_W)
         T2_LAUNCH(forward_sum_alpha_kernel<1>, dim3((unsigned)B), dim3(FS_W), 0, (hipStream_t)stream, scores, sb, st, t_len, n_len,
                   T_max, N_max, log_z, slab, offs, ld, stamps);
@@ -317,12 +316,12 @@ extern "C" int t2amd_forward_sum_bwd_f32(const float* scores, long long sb, long
     char msg[160];
     T2_REQUIRE(scores && t_len && n_len && log_z && grad && ws, "forward_sum_bwd: null operand");
     if (fs_check(B, T_max, N_max, msg) != T2AMD_OK) T2_FAIL(msg);
-    T2_REQUIRE(st >= N_max && (B == 1 || sb >= (T_max - 1) * st + N_max), "forward_sum_bwd: score strides shorter than the matrix");
-    T2_REQUIRE(gt >= N_max && (B == 1 || gb >= (T_max - 1) * gt + N_max), "forward_sum_bwd: gradient strides shorter than the matrix");
+    T2_REQUIRE(t2_strides_cover(sb, st, B, T_max, N_max), "forward_sum_bwd: score strides shorter than the matrix");
+    T2_REQUIRE(t2_strides_cover(gb, gt, B, T_max, N_max), "forward_sum_bwd: gradient strides shorter than the matrix");
     const long long kept = fs_kept_bytes(B, T_max, N_max);
     T2_REQUIRE(ws_bytes >= kept + 16LL * B, "forward_sum_bwd: the workspace is smaller than t2amd_forward_sum_workspace asks for");
     T2_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15u) == 0, "forward_sum_bwd: the workspace is not aligned to 16 bytes");
-    const long long sbytes = 4 * ((B - 1) * sb + (T_max - 1) * st + N_max), gbytes = 4 * ((B - 1) * gb + (T_max - 1) * gt + N_max);
+    const long long sbytes = t2_span_bytes(sb, st, B, T_max, N_max), gbytes = t2_span_bytes(gb, gt, B, T_max, N_max);
     T2_REQUIRE(!t2_overlap(grad, gbytes, scores, sbytes) && !t2_overlap(grad, gbytes, ws, ws_bytes) &&
                    !t2_overlap(grad, gbytes, log_z, 4LL * B) && !(scale && t2_overlap(grad, gbytes, scale, 4LL * B)) &&
                    !(soft && (t2_overlap(soft, 4LL * B * N_max, scores, sbytes) || t2_overlap(soft, 4LL * B * N_max, ws, ws_bytes) ||
@@ -331,7 +330,7 @@ extern "C" int t2amd_forward_sum_bwd_f32(const float* scores, long long sb, long
     const float* slab = reinterpret_cast<const float*>(ws);
     const double* offs = reinterpret_cast<const double*>(ws + fs_slab_bytes(B, T_max, N_max));
     unsigned long long* stamps = reinterpret_cast<unsigned long long*>(ws + kept);
-    const int ld = (int)fs_ld(N_max);
+    const int ld = (int)t2_round_up(N_max, 4);
     if (N_max <= FS_W)
         T2_LAUNCH(forward_sum_beta_kernel<1>, dim3((unsigned)B), dim3(FS_W), 0, (hipStream_t)stream, scores, sb, st, t_len, n_len,
                   T_max, N_max, log_z, scale, grad, gb, gt, soft, slab, offs, ld, stamps);

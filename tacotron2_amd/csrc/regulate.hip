@@ -192,13 +192,6 @@ static int rg_check(const char* who, int B, int N_max, int T, int C, int t_min) 
     T2_FAIL(msg);
 }
 
-// rows of `cols` floats at a row stride ld and a batch stride bs cover (B, R, cols)
-static inline bool rg_strides_ok(long long bs, long long ld, int B, int R, int cols) {
-    return ld >= cols && (B == 1 || bs >= (long long)(R - 1) * ld + cols);
-}
-static inline long long rg_bytes(long long bs, long long ld, int B, int R, int cols) {
-    return 4 * ((B - 1) * bs + (long long)(R - 1) * ld + cols);
-}
 static inline int rg_width(int C) {
     int w = 1;
     while (w < C && w < 64) w <<= 1;
@@ -239,8 +232,8 @@ extern "C" int t2amd_length_regulate_f32(const float* x, long long xb, long long
                                          float* y, void* stream) {
     T2_REQUIRE(x && path && y, "length_regulate: null operand");
     T2_PROPAGATE(rg_check("length_regulate", B, N_max, T, C, 1));
-    T2_REQUIRE(rg_strides_ok(xb, xn, B, N_max, C), "length_regulate: token strides shorter than the rows");
-    T2_REQUIRE(!t2_overlap(y, 4LL * B * T * C, x, rg_bytes(xb, xn, B, N_max, C)) && !t2_overlap(y, 4LL * B * T * C, path, 4LL * B * T),
+    T2_REQUIRE(t2_strides_cover(xb, xn, B, N_max, C), "length_regulate: token strides shorter than the rows");
+    T2_REQUIRE(!t2_overlap(y, 4LL * B * T * C, x, t2_span_bytes(xb, xn, B, N_max, C)) && !t2_overlap(y, 4LL * B * T * C, path, 4LL * B * T),
                "length_regulate: the output must not overlap the inputs");
     const bool vec = (C & 3) == 0 && t2_aligned16(x) && t2_aligned16(y) && (xn & 3) == 0 && (B == 1 || (xb & 3) == 0);
     const int cw = vec ? C / 4 : C, frames = RG_ITEMS / cw > 1 ? RG_ITEMS / cw : 1;
@@ -257,8 +250,8 @@ extern "C" int t2amd_length_regulate_bwd_f32(const float* dy, long long gb, long
                                              int C, float* dx, void* stream) {
     T2_REQUIRE(dy && ends && dx, "length_regulate_bwd: null operand");
     T2_PROPAGATE(rg_check("length_regulate_bwd", B, N_max, T, C, 1));
-    T2_REQUIRE(rg_strides_ok(gb, gt, B, T, C), "length_regulate_bwd: gradient strides shorter than the rows");
-    T2_REQUIRE(!t2_overlap(dx, 4LL * B * N_max * C, dy, rg_bytes(gb, gt, B, T, C)) &&
+    T2_REQUIRE(t2_strides_cover(gb, gt, B, T, C), "length_regulate_bwd: gradient strides shorter than the rows");
+    T2_REQUIRE(!t2_overlap(dx, 4LL * B * N_max * C, dy, t2_span_bytes(gb, gt, B, T, C)) &&
                    !t2_overlap(dx, 4LL * B * N_max * C, ends, 4LL * B * N_max),
                "length_regulate_bwd: the output must not overlap the inputs");
     const int width = rg_width(C);
@@ -272,9 +265,9 @@ extern "C" int t2amd_token_average_f32(const float* v, long long vb, long long v
                                        int B, int N_max, int T, int C, float* m, float* den, float* num, void* stream) {
     T2_REQUIRE(v && ends && m && den, "token_average: null operand");
     T2_PROPAGATE(rg_check("token_average", B, N_max, T, C, 1));
-    T2_REQUIRE(rg_strides_ok(vb, vt, B, T, C), "token_average: value strides shorter than the rows");
+    T2_REQUIRE(t2_strides_cover(vb, vt, B, T, C), "token_average: value strides shorter than the rows");
     T2_REQUIRE(!w || B == 1 || wb >= T, "token_average: the weight stride is shorter than a row");
-    const long long vbytes = rg_bytes(vb, vt, B, T, C), wbytes = 4 * ((B - 1) * wb + T), obytes = 4LL * B * N_max * C;
+    const long long vbytes = t2_span_bytes(vb, vt, B, T, C), wbytes = 4 * ((B - 1) * wb + T), obytes = 4LL * B * N_max * C;
     T2_REQUIRE(!t2_overlap(m, obytes, v, vbytes) && !t2_overlap(den, 4LL * B * N_max, v, vbytes) &&
                    !t2_overlap(m, obytes, ends, 4LL * B * N_max) && !t2_overlap(den, 4LL * B * N_max, ends, 4LL * B * N_max) &&
                    !t2_overlap(m, obytes, den, 4LL * B * N_max) &&

@@ -23,12 +23,11 @@ struct SaOperand {
     long long sb, st, sh;
 };
 
-static inline long long sa_r4(long long n) { return (n + 3) / 4 * 4; }
-static inline long long sa_rows_bytes(int B, int T, int H) { return 4 * sa_r4((long long)B * H * T); }
+static inline long long sa_rows_bytes(int B, int T, int H) { return 4 * t2_round_up((long long)B * H * T, 4); }
 
 // bytes from the operand's base to the end of its last row
 static inline long long sa_span(const SaOperand& x, int B, int T, int H, int D) {
-    return 4 * ((B - 1) * x.sb + (T - 1) * x.st + (H - 1) * x.sh + D);
+    return t2_span_bytes(x.sb, x.st, B, T, (H - 1) * x.sh + D);
 }
 
 // the limits every entry shares; `who` is the entry's name inside the error text

@@ -1900,6 +1900,70 @@ def _pair_lengths(who, n, B):
     return None if n is None else ptr(n, torch.int32)
 
 
+# ---- argument helpers of the ragged ops: a padded batch, per-utterance lengths, strided float32 operands, a uint8 workspace ----------
+# Two stride conventions, because the C entries check two things.  The path, aligner and regulator entries ask for strides that
+# cover the matrix (``_cover_strides``); the matrix-pipe entries of self-attention and the FFT block ask for 16-byte bases and
+# strides in multiples of 4 floats, and take 0 for an axis of one element (``_operand``).
+def _cover(x):
+    """(batch stride, row stride) of a rank-3 tensor; an axis of one element gets a stride that covers what it holds."""
+    B, R, cols = x.shape
+    sr = x.stride(1) if R > 1 else max(x.stride(1), cols)
+    sb = x.stride(0) if B > 1 else max(x.stride(0), (R - 1) * sr + cols)
+    return sb, sr
+
+
+def _cover_strides(who, x, what, along):
+    """``_cover`` of a rank-3 tensor without an empty axis and with unit stride on its last one; ``what`` names it in the refusal,
+    as in "(B, T, N) scores", and ``along`` is the last axis' letter."""
+    if x.dim() != 3 or min(x.shape) < 1 or (x.shape[2] > 1 and x.stride(2) != 1):
+        raise NativeError("%s: expected %s with unit stride along %s, got shape %s stride %s" % (who, what, along, tuple(x.shape), x.stride()))
+    return _cover(x)
+
+
+def _operand(who, x, name, axes, shape=None):
+    """[pointer, stride of every axis but the last] of a float32 tensor of the rank ``axes`` spells out, "(B, T, H, D)" or
+    "(B, T, C)", with unit stride along the last axis; an axis of one element has no stride."""
+    n = axes.count(",")
+    if x.dim() != n + 1 or min(x.shape) < 1 or x.stride(n) != 1 or (shape is not None and tuple(x.shape) != tuple(shape)):
+        raise NativeError("%s: expected %s %s%s with unit stride along %s, got shape %s stride %s"
+                          % (who, name, axes, "" if shape is None else " = %s" % (tuple(shape),), axes[-2], tuple(x.shape), x.stride()))
+    return [ptr(x)] + [_i64(x.stride(i) if x.shape[i] > 1 else 0) for i in range(n)]
+
+
+def _exact(who, t, name, shape, dtype=None):
+    """Pointer of ``t``: None, or a contiguous tensor of exactly ``shape``.  The integer operands name their ``dtype`` and the
+    refusal says which came instead; without one ``t`` is float32, and a wrong dtype is ``ptr``'s to refuse."""
+    if t is None:
+        return None
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or (dtype is not None and t.dtype != dtype):
+        if dtype is None:
+            raise NativeError("%s: expected contiguous %s %s, got shape %s stride %s" % (who, name, tuple(shape), tuple(t.shape), t.stride()))
+        raise NativeError("%s: expected contiguous %s %s of shape %s, got %s %s"
+                          % (who, str(dtype).replace("torch.", ""), name, tuple(shape), t.dtype, tuple(t.shape)))
+    return ptr(t, dtype or torch.float32)
+
+
+def _workspace(who, ws):
+    """(pointer, bytes) of a workspace: a contiguous uint8 tensor."""
+    if ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise NativeError("%s: the workspace must be a contiguous uint8 tensor, got %s" % (who, ws.dtype))
+    return ptr(ws, torch.uint8), _i64(ws.numel())
+
+
+def _query_ints(entry, n, *args):
+    """The n ints the C query ``entry`` writes behind its arguments."""
+    v = [C.c_int(0) for _ in range(n)]
+    _check(getattr(load(), entry)(*args, *[C.byref(x) for x in v]), entry)
+    return tuple(x.value for x in v)
+
+
+def _query_bytes(entry, *args):
+    """The one long long (a workspace's bytes) the C query ``entry`` writes behind its arguments."""
+    n = C.c_longlong(0)
+    _check(getattr(load(), entry)(*args, C.byref(n)), entry)
+    return n.value
+
+
 def mel_cepstrum(mel, lengths, basis, out):
     """out (B, T, K) = the cepstra of the log-mel ``mel`` (B, n_mel, T) (unit stride along T) under ``basis`` (K, n_mel); rows at
     and beyond ``lengths`` (device int32 or None) are zeros."""
@@ -1908,8 +1972,7 @@ def mel_cepstrum(mel, lengths, basis, out):
         raise NativeError("mel_cepstrum: shape mismatch mel=%s stride %s basis=%s out=%s"
                           % (tuple(mel.shape), mel.stride(), tuple(basis.shape), tuple(out.shape)))
     B, N, T = mel.shape
-    ldm = mel.stride(1) if N > 1 else max(mel.stride(1), T)
-    ldb = mel.stride(0) if B > 1 else max(mel.stride(0), (N - 1) * ldm + T)
+    ldb, ldm = _cover(mel)
     _check(load().t2amd_mel_cepstrum_f32(ptr(mel), _i64(ldb), _i64(ldm), _pair_lengths("mel_cepstrum", lengths, B), B, N, T,
                                          ptr(_fullc(basis)), int(basis.shape[0]), ptr(_fullc(out)), _stream()),
            "t2amd_mel_cepstrum_f32")
@@ -1951,10 +2014,7 @@ def dtw_backtrack(slab, na, nb, steps, Ta, Tb, out):
 # ---- F0 extraction by YIN (csrc/yin.hip) -------------------------------------------------------------------------------------------
 def yin_plan(sr, frame_length, hop_length, fmin, fmax):
     """-> (tau_min, tau_max) = (floor(sr / fmax), ceil(sr / fmin)) of a YIN geometry; NativeError where the library refuses it."""
-    lo, hi = C.c_int(0), C.c_int(0)
-    _check(load().t2amd_yin_plan(float(sr), int(frame_length), int(hop_length), float(fmin), float(fmax), C.byref(lo), C.byref(hi)),
-           "t2amd_yin_plan")
-    return lo.value, hi.value
+    return _query_ints("t2amd_yin_plan", 2, float(sr), int(frame_length), int(hop_length), float(fmin), float(fmax))
 
 
 def yin(x, lengths, frame_length, hop_length, tau_min, tau_max, sr, threshold, f0, voiced, aperiodicity, dprime=None):
@@ -1977,75 +2037,50 @@ def yin(x, lengths, frame_length, hop_length, tau_min, tau_max, sr, threshold, f
 # ---- forced alignment: the best monotonic path (csrc/align.hip) ------------------------------------------------------------------
 def align_limits():
     """-> (lanes of the workgroup, frames at most, tokens at most) of ``monotonic_align``."""
-    w, t, n = C.c_int(0), C.c_int(0), C.c_int(0)
-    _check(load().t2amd_align_limits(C.byref(w), C.byref(t), C.byref(n)), "t2amd_align_limits")
-    return w.value, t.value, n.value
+    return _query_ints("t2amd_align_limits", 3)
 
 
 def align_workspace(B, T_max, N_max):
     """Bytes of the workspace ``monotonic_align`` needs for B utterances of at most T_max frames and N_max tokens."""
-    n = C.c_longlong(0)
-    _check(load().t2amd_align_workspace(int(B), int(T_max), int(N_max), C.byref(n)), "t2amd_align_workspace")
-    return n.value
+    return _query_bytes("t2amd_align_workspace", int(B), int(T_max), int(N_max))
 
 
 def monotonic_align(scores, t_len, n_len, durations, score, path, ws):
     """durations (B, N) int32, score (B,) float32 and, unless None, path (B, T) int32 of the best monotonic path through each
     scores[b, :t_len[b], :n_len[b]] of the (B, T, N) float32 ``scores`` (unit stride along N; device int32 lengths); ``ws`` is a
     uint8 tensor of at least ``align_workspace(B, T, N)`` bytes."""
-    if scores.dim() != 3 or min(scores.shape) < 1 or (scores.shape[2] > 1 and scores.stride(2) != 1):
-        raise NativeError("monotonic_align: expected (B, T, N) scores with unit stride along N, got shape %s stride %s"
-                          % (tuple(scores.shape), scores.stride()))
+    who = "monotonic_align"
+    sb, st = _cover_strides(who, scores, "(B, T, N) scores", "N")
     B, T, N = scores.shape
-    st = scores.stride(1) if T > 1 else max(scores.stride(1), N)
-    sb = scores.stride(0) if B > 1 else max(scores.stride(0), (T - 1) * st + N)
     if tuple(durations.shape) != (B, N) or score.numel() != B or (path is not None and tuple(path.shape) != (B, T)):
         raise NativeError("monotonic_align: expected durations (%d, %d), score (%d,) and path (%d, %d), got %s, %s and %s"
                           % (B, N, B, B, T, tuple(durations.shape), tuple(score.shape), None if path is None else tuple(path.shape)))
-    if ws.dtype != torch.uint8 or not ws.is_contiguous():
-        raise NativeError("monotonic_align: the workspace must be a contiguous uint8 tensor, got %s" % ws.dtype)
-    _check(load().t2amd_monotonic_align_f32(ptr(scores), _i64(sb), _i64(st), _pair_lengths("monotonic_align", t_len, B),
-                                            _pair_lengths("monotonic_align", n_len, B), B, T, N,
-                                            ptr(_fullc(durations), torch.int32), ptr(_fullc(score)),
-                                            None if path is None else ptr(_fullc(path), torch.int32), ptr(ws, torch.uint8),
-                                            _i64(ws.numel()), _stream()), "t2amd_monotonic_align_f32")
+    pw, nw = _workspace(who, ws)
+    _check(load().t2amd_monotonic_align_f32(ptr(scores), _i64(sb), _i64(st), _pair_lengths(who, t_len, B), _pair_lengths(who, n_len, B),
+                                            B, T, N, ptr(_fullc(durations), torch.int32), ptr(_fullc(score)),
+                                            None if path is None else ptr(_fullc(path), torch.int32), pw, nw, _stream()),
+           "t2amd_monotonic_align_f32")
 
 
 # ---- forward-sum alignment likelihood and its gradient (csrc/forward_sum.hip) ---------------------------------------------------
+_BTN = ("a (B, T, N) tensor", "N")                                         # how the forward-sum and aligner refusals name a matrix
+
+
 def forward_sum_workspace(B, T_max, N_max, keep=True):
     """Bytes of the workspace ``forward_sum`` needs for B utterances of at most T_max frames and N_max tokens; with ``keep`` it
     holds the alpha rows ``forward_sum_backward`` reads."""
-    n = C.c_longlong(0)
-    _check(load().t2amd_forward_sum_workspace(int(B), int(T_max), int(N_max), 1 if keep else 0, C.byref(n)),
-           "t2amd_forward_sum_workspace")
-    return n.value
-
-
-def _forward_sum_strides(who, x):
-    if x.dim() != 3 or min(x.shape) < 1 or (x.shape[2] > 1 and x.stride(2) != 1):
-        raise NativeError("%s: expected a (B, T, N) tensor with unit stride along N, got shape %s stride %s"
-                          % (who, tuple(x.shape), x.stride()))
-    B, T, N = x.shape
-    st = x.stride(1) if T > 1 else max(x.stride(1), N)
-    sb = x.stride(0) if B > 1 else max(x.stride(0), (T - 1) * st + N)
-    return sb, st
-
-
-def _forward_sum_ws(who, ws):
-    if ws.dtype != torch.uint8 or not ws.is_contiguous():
-        raise NativeError("%s: the workspace must be a contiguous uint8 tensor, got %s" % (who, ws.dtype))
-    return ptr(ws, torch.uint8), _i64(ws.numel())
+    return _query_bytes("t2amd_forward_sum_workspace", int(B), int(T_max), int(N_max), 1 if keep else 0)
 
 
 def forward_sum(scores, t_len, n_len, log_z, ws, keep=True):
     """log_z (B,) float32 = the log of the summed probability of all monotonic paths through each scores[b, :t_len[b], :n_len[b]]
     of the (B, T, N) float32 ``scores`` (unit stride along N; device int32 lengths); ``ws`` is a uint8 tensor of at least
     ``forward_sum_workspace(B, T, N, keep)`` bytes, and with ``keep`` it leaves holding what ``forward_sum_backward`` reads."""
-    sb, st = _forward_sum_strides("forward_sum", scores)
+    sb, st = _cover_strides("forward_sum", scores, *_BTN)
     B, T, N = scores.shape
     if log_z.numel() != B:
         raise NativeError("forward_sum: expected log_z (%d,), got %s" % (B, tuple(log_z.shape)))
-    pw, nw = _forward_sum_ws("forward_sum", ws)
+    pw, nw = _workspace("forward_sum", ws)
     _check(load().t2amd_forward_sum_f32(ptr(scores), _i64(sb), _i64(st), _pair_lengths("forward_sum", t_len, B),
                                         _pair_lengths("forward_sum", n_len, B), B, T, N, ptr(_fullc(log_z)), 1 if keep else 0,
                                         pw, nw, _stream()), "t2amd_forward_sum_f32")
@@ -2055,15 +2090,15 @@ def forward_sum_backward(scores, t_len, n_len, log_z, scale, grad, soft, ws):
     """grad (B, T, N) float32 (unit stride along N) = scale[b] (None: 1) times the posterior occupancy of every cell, zeros in an
     utterance's padding, and, unless None, soft (B, N) float32 = its column sums; ``scores``, the lengths, ``log_z`` and ``ws``
     are those of a ``forward_sum(..., keep=True)`` call."""
-    sb, st = _forward_sum_strides("forward_sum_backward", scores)
-    gb, gt = _forward_sum_strides("forward_sum_backward", grad)
+    sb, st = _cover_strides("forward_sum_backward", scores, *_BTN)
+    gb, gt = _cover_strides("forward_sum_backward", grad, *_BTN)
     B, T, N = scores.shape
     if tuple(grad.shape) != (B, T, N) or log_z.numel() != B or (scale is not None and scale.numel() != B) \
             or (soft is not None and tuple(soft.shape) != (B, N)):
         raise NativeError("forward_sum_backward: expected grad (%d, %d, %d), log_z and scale (%d,) and soft (%d, %d), got %s, %s, %s "
                           "and %s" % (B, T, N, B, B, N, tuple(grad.shape), tuple(log_z.shape),
                                       None if scale is None else tuple(scale.shape), None if soft is None else tuple(soft.shape)))
-    pw, nw = _forward_sum_ws("forward_sum_backward", ws)
+    pw, nw = _workspace("forward_sum_backward", ws)
     _check(load().t2amd_forward_sum_bwd_f32(ptr(scores), _i64(sb), _i64(st), _pair_lengths("forward_sum_backward", t_len, B),
                                             _pair_lengths("forward_sum_backward", n_len, B), B, T, N, ptr(_fullc(log_z)),
                                             None if scale is None else ptr(_fullc(scale)), ptr(grad), _i64(gb), _i64(gt),
@@ -2075,9 +2110,7 @@ def forward_sum_backward(scores, t_len, n_len, log_z, scale, grad, soft, ws):
 def aligner_workspace(B, T_max, N_max, C_, which=0):
     """Bytes of a workspace of the aligner scores for B utterances of at most T_max frames and N_max tokens of C_ channels:
     ``which`` 0 the forward's, 1 the forward's with what the backward reads kept, 2 the backward's own."""
-    n = C.c_longlong(0)
-    _check(load().t2amd_aligner_workspace(int(B), int(T_max), int(N_max), int(C_), int(which), C.byref(n)), "t2amd_aligner_workspace")
-    return n.value
+    return _query_bytes("t2amd_aligner_workspace", int(B), int(T_max), int(N_max), int(C_), int(which))
 
 
 def _aligner_operands(who, q, k):
@@ -2091,37 +2124,37 @@ def aligner_scores(q, k, t_len, n_len, tau, log_prior, scores, ws, keep=False):
     (B, T, N) or None, -inf in every utterance's padding; q (B, T, C) and k (B, N, C) contiguous float32, device int32 lengths;
     ``ws`` is a uint8 tensor of at least ``aligner_workspace(B, T, N, C, keep)`` bytes, and with ``keep`` it leaves holding what
     ``aligner_scores_backward`` reads."""
-    B, T, N, C_ = _aligner_operands("aligner_scores", q, k)
+    who = "aligner_scores"
+    B, T, N, C_ = _aligner_operands(who, q, k)
     if tuple(scores.shape) != (B, T, N) or (log_prior is not None and tuple(log_prior.shape) != (B, T, N)):
         raise NativeError("aligner_scores: expected scores and log_prior (%d, %d, %d), got %s and %s"
                           % (B, T, N, tuple(scores.shape), None if log_prior is None else tuple(log_prior.shape)))
-    sb, st = _forward_sum_strides("aligner_scores", scores)
-    pb, pt = (0, 0) if log_prior is None else _forward_sum_strides("aligner_scores", log_prior)
-    pw, nw = _forward_sum_ws("aligner_scores", ws)
-    _check(load().t2amd_aligner_scores_f32(ptr(_fullc(q)), ptr(_fullc(k)), _pair_lengths("aligner_scores", t_len, B),
-                                           _pair_lengths("aligner_scores", n_len, B), B, T, N, C_, float(tau), ptr(log_prior),
-                                           _i64(pb), _i64(pt), ptr(scores), _i64(sb), _i64(st), 1 if keep else 0, pw, nw, _stream()),
-           "t2amd_aligner_scores_f32")
+    sb, st = _cover_strides(who, scores, *_BTN)
+    pb, pt = (0, 0) if log_prior is None else _cover_strides(who, log_prior, *_BTN)
+    pw, nw = _workspace(who, ws)
+    _check(load().t2amd_aligner_scores_f32(ptr(_fullc(q)), ptr(_fullc(k)), _pair_lengths(who, t_len, B), _pair_lengths(who, n_len, B),
+                                           B, T, N, C_, float(tau), ptr(log_prior), _i64(pb), _i64(pt), ptr(scores), _i64(sb), _i64(st),
+                                           1 if keep else 0, pw, nw, _stream()), "t2amd_aligner_scores_f32")
 
 
 def aligner_scores_backward(q, k, t_len, n_len, tau, grad, dq, dk, dlogp, kept, ws):
     """dq (B, T, C), dk (B, N, C) contiguous float32 and, unless None, dlogp (B, T, N) from ``grad`` = dL/dscores (B, T, N) (unit
     stride along N), exact zeros in every utterance's padding; ``kept`` is the workspace of an ``aligner_scores(..., keep=True)``
     call on the same operands, ``ws`` a uint8 tensor of at least ``aligner_workspace(B, T, N, C, 2)`` bytes."""
-    B, T, N, C_ = _aligner_operands("aligner_scores_backward", q, k)
+    who = "aligner_scores_backward"
+    B, T, N, C_ = _aligner_operands(who, q, k)
     if tuple(grad.shape) != (B, T, N) or tuple(dq.shape) != (B, T, C_) or tuple(dk.shape) != (B, N, C_) \
             or (dlogp is not None and tuple(dlogp.shape) != (B, T, N)):
         raise NativeError("aligner_scores_backward: expected grad and dlogp (%d, %d, %d), dq (%d, %d, %d) and dk (%d, %d, %d), got "
                           "%s, %s, %s and %s" % (B, T, N, B, T, C_, B, N, C_, tuple(grad.shape),
                                                  None if dlogp is None else tuple(dlogp.shape), tuple(dq.shape), tuple(dk.shape)))
-    gb, gt = _forward_sum_strides("aligner_scores_backward", grad)
-    db, dt = (0, 0) if dlogp is None else _forward_sum_strides("aligner_scores_backward", dlogp)
-    pk, nk = _forward_sum_ws("aligner_scores_backward", kept)
-    pw, nw = _forward_sum_ws("aligner_scores_backward", ws)
-    _check(load().t2amd_aligner_scores_bwd_f32(ptr(_fullc(q)), ptr(_fullc(k)), _pair_lengths("aligner_scores_backward", t_len, B),
-                                               _pair_lengths("aligner_scores_backward", n_len, B), B, T, N, C_, float(tau), ptr(grad),
-                                               _i64(gb), _i64(gt), ptr(_fullc(dq)), ptr(_fullc(dk)), ptr(dlogp), _i64(db), _i64(dt),
-                                               pk, nk, pw, nw, _stream()), "t2amd_aligner_scores_bwd_f32")
+    gb, gt = _cover_strides(who, grad, *_BTN)
+    db, dt = (0, 0) if dlogp is None else _cover_strides(who, dlogp, *_BTN)
+    pk, nk = _workspace(who, kept)
+    pw, nw = _workspace(who, ws)
+    _check(load().t2amd_aligner_scores_bwd_f32(ptr(_fullc(q)), ptr(_fullc(k)), _pair_lengths(who, t_len, B), _pair_lengths(who, n_len, B),
+                                               B, T, N, C_, float(tau), ptr(grad), _i64(gb), _i64(gt), ptr(_fullc(dq)), ptr(_fullc(dk)),
+                                               ptr(dlogp), _i64(db), _i64(dt), pk, nk, pw, nw, _stream()), "t2amd_aligner_scores_bwd_f32")
 
 
 def beta_binomial_log_prior(t_len, n_len, scaling, out):
@@ -2138,26 +2171,7 @@ def beta_binomial_log_prior(t_len, n_len, scaling, out):
 # ---- the length regulator: durations -> path, expansion, pooling and their gradients (csrc/regulate.hip) --------------------------
 def regulate_limits():
     """-> (channels at most, tokens at most, frames at most) of the length regulator."""
-    c, n, t = C.c_int(0), C.c_int(0), C.c_int(0)
-    _check(load().t2amd_regulate_limits(C.byref(c), C.byref(n), C.byref(t)), "t2amd_regulate_limits")
-    return c.value, n.value, t.value
-
-
-def _regulate_rows(who, x, what):
-    """Strides (batch, row) of a (B, R, C) float32 tensor with unit stride along C."""
-    if x.dim() != 3 or min(x.shape) < 1 or (x.shape[2] > 1 and x.stride(2) != 1):
-        raise NativeError("%s: expected (B, rows, C) %s with unit stride along C, got shape %s stride %s"
-                          % (who, what, tuple(x.shape), x.stride()))
-    B, R, C_ = x.shape
-    sr = x.stride(1) if R > 1 else max(x.stride(1), C_)
-    sb = x.stride(0) if B > 1 else max(x.stride(0), (R - 1) * sr + C_)
-    return sb, sr
-
-
-def _regulate_ints(who, t, shape, name):
-    if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
-        raise NativeError("%s: expected contiguous int32 %s of shape %s, got %s %s" % (who, name, tuple(shape), t.dtype, tuple(t.shape)))
-    return None if t is None else ptr(t, torch.int32)
+    return _query_ints("t2amd_regulate_limits", 3)
 
 
 def durations_to_path(durations, n_len, T, path, t_lengths, ends=None, totals=None):
@@ -2175,34 +2189,37 @@ def durations_to_path(durations, n_len, T, path, t_lengths, ends=None, totals=No
     if totals is not None and (totals.dtype != torch.int64 or tuple(totals.shape) != (B,) or not totals.is_contiguous()):
         raise NativeError("%s: expected contiguous int64 totals of shape (%d,)" % (who, B))
     _check(load().t2amd_durations_to_path_i32(ptr(durations, None), durations.element_size(), _i64(db), _pair_lengths(who, n_len, B),
-                                              B, N, int(T), _regulate_ints(who, path, (B, int(T)), "path"),
-                                              _regulate_ints(who, t_lengths, (B,), "t_lengths"), _regulate_ints(who, ends, (B, N), "ends"),
+                                              B, N, int(T), _exact(who, path, "path", (B, int(T)), torch.int32),
+                                              _exact(who, t_lengths, "t_lengths", (B,), torch.int32),
+                                              _exact(who, ends, "ends", (B, N), torch.int32),
                                               None if totals is None else ptr(totals, torch.int64), _stream()),
            "t2amd_durations_to_path_i32")
 
 
 def length_regulate(x, path, y):
     """y (B, T, C) contiguous float32: y[b, t] = x[b, path[b, t]], +0 where path is -1; x (B, N, C), unit stride along C."""
-    xb, xn = _regulate_rows("length_regulate", x, "tokens")
+    who = "length_regulate"
+    xb, xn = _cover_strides(who, x, "(B, rows, C) tokens", "C")
     B, N, C_ = x.shape
     if y.dim() != 3 or y.shape[0] != B or y.shape[2] != C_ or tuple(path.shape) != tuple(y.shape[:2]):
         raise NativeError("length_regulate: expected y (%d, T, %d) and path (%d, T), got %s and %s"
                           % (B, C_, B, tuple(y.shape), tuple(path.shape)))
     T = y.shape[1]
-    _check(load().t2amd_length_regulate_f32(ptr(x), _i64(xb), _i64(xn), _regulate_ints("length_regulate", path, (B, T), "path"), B, N,
-                                            T, C_, ptr(_fullc(y)), _stream()), "t2amd_length_regulate_f32")
+    _check(load().t2amd_length_regulate_f32(ptr(x), _i64(xb), _i64(xn), _exact(who, path, "path", (B, T), torch.int32), B, N, T, C_,
+                                            ptr(_fullc(y)), _stream()), "t2amd_length_regulate_f32")
 
 
 def length_regulate_backward(dy, ends, dx):
     """dx (B, N, C) contiguous float32: the sum of dy (B, T, C) (unit stride along C) over each token's frames, ascending; ``ends``
     (B, N) int32 as ``durations_to_path`` wrote it."""
-    gb, gt = _regulate_rows("length_regulate_backward", dy, "gradient")
+    who = "length_regulate_backward"
+    gb, gt = _cover_strides(who, dy, "(B, rows, C) gradient", "C")
     B, T, C_ = dy.shape
     if dx.dim() != 3 or dx.shape[0] != B or dx.shape[2] != C_:
         raise NativeError("length_regulate_backward: expected dx (%d, N, %d), got %s" % (B, C_, tuple(dx.shape)))
     N = dx.shape[1]
-    _check(load().t2amd_length_regulate_bwd_f32(ptr(dy), _i64(gb), _i64(gt), _regulate_ints("length_regulate_backward", ends, (B, N), "ends"),
-                                                B, N, T, C_, ptr(_fullc(dx)), _stream()), "t2amd_length_regulate_bwd_f32")
+    _check(load().t2amd_length_regulate_bwd_f32(ptr(dy), _i64(gb), _i64(gt), _exact(who, ends, "ends", (B, N), torch.int32), B, N, T, C_,
+                                                ptr(_fullc(dx)), _stream()), "t2amd_length_regulate_bwd_f32")
 
 
 def _regulate_weights(who, w, B, T):
@@ -2218,7 +2235,7 @@ def token_average(values, weights, ends, mean, den, num=None):
     """mean (B, N, C) and den (B, N) contiguous float32, and unless None num (B, N, C): the weighted sums of values (B, T, C) (unit
     stride along C) over each token's frames, the sums of the weights (B, T) (None: ones), and their quotient (+0 where den = 0)."""
     who = "token_average"
-    vb, vt = _regulate_rows(who, values, "values")
+    vb, vt = _cover_strides(who, values, "(B, rows, C) values", "C")
     B, T, C_ = values.shape
     if mean.dim() != 3 or mean.shape[0] != B or mean.shape[2] != C_ or tuple(den.shape) != tuple(mean.shape[:2]) \
             or (num is not None and tuple(num.shape) != tuple(mean.shape)):
@@ -2226,8 +2243,8 @@ def token_average(values, weights, ends, mean, den, num=None):
                           % (who, B, C_, B, tuple(mean.shape), None if num is None else tuple(num.shape), tuple(den.shape)))
     N = mean.shape[1]
     pw, wb = _regulate_weights(who, weights, B, T)
-    _check(load().t2amd_token_average_f32(ptr(values), _i64(vb), _i64(vt), pw, _i64(wb), _regulate_ints(who, ends, (B, N), "ends"), B, N,
-                                          T, C_, ptr(_fullc(mean)), ptr(_fullc(den)), None if num is None else ptr(_fullc(num)),
+    _check(load().t2amd_token_average_f32(ptr(values), _i64(vb), _i64(vt), pw, _i64(wb), _exact(who, ends, "ends", (B, N), torch.int32),
+                                          B, N, T, C_, ptr(_fullc(mean)), ptr(_fullc(den)), None if num is None else ptr(_fullc(num)),
                                           _stream()), "t2amd_token_average_f32")
 
 
@@ -2243,38 +2260,23 @@ def token_average_backward(grad, den, weights, path, dv):
     T = dv.shape[1]
     pw, wb = _regulate_weights(who, weights, B, T)
     _check(load().t2amd_token_average_bwd_f32(ptr(_fullc(grad)), ptr(_fullc(den)), pw, _i64(wb),
-                                              _regulate_ints(who, path, (B, T), "path"), B, N, T, C_, ptr(_fullc(dv)), _stream()),
+                                              _exact(who, path, "path", (B, T), torch.int32), B, N, T, C_, ptr(_fullc(dv)), _stream()),
            "t2amd_token_average_bwd_f32")
 
 
 # ---- masked multi-head self-attention and its gradient (csrc/self_attn.hip, csrc/self_attn_rows.hip) -----------------------------
+_BTHD = "(B, T, H, D)"
+
+
 def self_attn_limits():
     """-> (frames at most, heads at most, least head width, greatest head width, utterances times heads at most)."""
-    v = [C.c_int(0) for _ in range(5)]
-    _check(load().t2amd_self_attn_limits(*[C.byref(x) for x in v]), "t2amd_self_attn_limits")
-    return tuple(x.value for x in v)
+    return _query_ints("t2amd_self_attn_limits", 5)
 
 
 def self_attn_workspace(B, T, H, D, which=0):
     """Bytes for B utterances of at most T frames, H heads of width D: ``which`` 0 the forward's workspace (none), 1 the lse the
     forward keeps for a backward, 2 the backward's workspace."""
-    n = C.c_longlong(0)
-    _check(load().t2amd_self_attn_workspace(int(B), int(T), int(H), int(D), int(which), C.byref(n)), "t2amd_self_attn_workspace")
-    return n.value
-
-
-def _self_attn_operand(who, x, name, shape=None):
-    """(pointer, batch stride, time stride, head stride) of a (B, T, H, D) float32 tensor with unit stride along D."""
-    if x.dim() != 4 or min(x.shape) < 1 or x.stride(3) != 1 or (shape is not None and tuple(x.shape) != tuple(shape)):
-        raise NativeError("%s: expected %s (B, T, H, D)%s with unit stride along D, got shape %s stride %s"
-                          % (who, name, "" if shape is None else " = %s" % (tuple(shape),), tuple(x.shape), x.stride()))
-    return [ptr(x)] + [_i64(x.stride(i) if x.shape[i] > 1 else 0) for i in range(3)]       # an axis of one element has no stride
-
-
-def _self_attn_rows(who, x, name, B, H, T):
-    if x is not None and (tuple(x.shape) != (B, H, T) or not x.is_contiguous()):
-        raise NativeError("%s: expected contiguous %s (%d, %d, %d), got shape %s stride %s" % (who, name, B, H, T, tuple(x.shape), x.stride()))
-    return ptr(x)
+    return _query_bytes("t2amd_self_attn_workspace", int(B), int(T), int(H), int(D), int(which))
 
 
 def self_attn(q, k, v, lengths, scale, o, lse=None):
@@ -2282,23 +2284,23 @@ def self_attn(q, k, v, lengths, scale, o, lse=None):
     int32, clamped; None: T), +0 at and beyond them; q, k, v (B, T, H, D) float32 with unit stride along D, the other strides
     multiples of 4 floats and 16-byte bases; ``lse`` (B, H, T) or None receives the row logsumexp a backward reads."""
     who = "self_attn"
-    aq = _self_attn_operand(who, q, "q")
+    aq = _operand(who, q, "q", _BTHD)
     B, T, H, D = q.shape
-    ak, av = _self_attn_operand(who, k, "k", q.shape), _self_attn_operand(who, v, "v", q.shape)
-    _self_attn_operand(who, o, "o", q.shape)
+    ak, av = _operand(who, k, "k", _BTHD, q.shape), _operand(who, v, "v", _BTHD, q.shape)
+    _operand(who, o, "o", _BTHD, q.shape)
     _check(load().t2amd_self_attn_f32(*(aq + ak + av + [_pair_lengths(who, lengths, B), B, T, H, D, float(scale), ptr(_fullc(o)),
-                                                         _self_attn_rows(who, lse, "lse", B, H, T), _stream()])),
+                                                         _exact(who, lse, "lse", (B, H, T)), _stream()])),
            "t2amd_self_attn_f32")
 
 
 def self_attn_delta(g, o, lengths, delta):
     """delta (B, H, T) contiguous float32 = sum_d g o per row, +0 at and beyond an utterance's frames: the backward's row pass."""
     who = "self_attn_delta"
-    ag = _self_attn_operand(who, g, "the gradient")
+    ag = _operand(who, g, "the gradient", _BTHD)
     B, T, H, D = g.shape
-    _self_attn_operand(who, o, "o", g.shape)
+    _operand(who, o, "o", _BTHD, g.shape)
     _check(load().t2amd_self_attn_delta_f32(*(ag + [ptr(_fullc(o)), _pair_lengths(who, lengths, B), B, T, H, D,
-                                                     _self_attn_rows(who, delta, "delta", B, H, T), _stream()])),
+                                                     _exact(who, delta, "delta", (B, H, T)), _stream()])),
            "t2amd_self_attn_delta_f32")
 
 
@@ -2306,15 +2308,15 @@ def self_attn_backward(q, k, v, o, lse, g, lengths, scale, dq, dk, dv, ws):
     """dq, dk, dv (B, T, H, D) contiguous float32 from ``g`` = dL/do (strided as q, k, v may be); ``o`` and ``lse`` are those of a
     ``self_attn`` call on the same operands, ``ws`` a uint8 tensor of at least ``self_attn_workspace(B, T, H, D, 2)`` bytes."""
     who = "self_attn_backward"
-    aq = _self_attn_operand(who, q, "q")
+    aq = _operand(who, q, "q", _BTHD)
     B, T, H, D = q.shape
-    ak, av = _self_attn_operand(who, k, "k", q.shape), _self_attn_operand(who, v, "v", q.shape)
-    ag = _self_attn_operand(who, g, "the gradient", q.shape)
+    ak, av = _operand(who, k, "k", _BTHD, q.shape), _operand(who, v, "v", _BTHD, q.shape)
+    ag = _operand(who, g, "the gradient", _BTHD, q.shape)
     for name, t in (("o", o), ("dq", dq), ("dk", dk), ("dv", dv)):
-        _self_attn_operand(who, t, name, q.shape)
+        _operand(who, t, name, _BTHD, q.shape)
         _fullc(t)
-    pw, nw = _forward_sum_ws(who, ws)
-    _check(load().t2amd_self_attn_bwd_f32(*(aq + ak + av + [ptr(o), _self_attn_rows(who, lse, "lse", B, H, T)] + ag
+    pw, nw = _workspace(who, ws)
+    _check(load().t2amd_self_attn_bwd_f32(*(aq + ak + av + [ptr(o), _exact(who, lse, "lse", (B, H, T))] + ag
                                             + [_pair_lengths(who, lengths, B), B, T, H, D, float(scale), ptr(dq), ptr(dk), ptr(dv),
                                                pw, nw, _stream()])), "t2amd_self_attn_bwd_f32")
 
@@ -2322,31 +2324,13 @@ def self_attn_backward(q, k, v, o, lse, g, lengths, scale, dq, dk, dv, ws):
 # ---- the feed-forward Transformer block's convolutional feed-forward and add + LayerNorm (csrc/fft_block.hip, fft_block_rows.hip) ----
 def fft_block_limits():
     """-> (frames at most, channels at most, kernel width at most, least LayerNorm width, utterances at most)."""
-    v = [C.c_int(0) for _ in range(5)]
-    _check(load().t2amd_fft_block_limits(*[C.byref(x) for x in v]), "t2amd_fft_block_limits")
-    return tuple(x.value for x in v)
+    return _query_ints("t2amd_fft_block_limits", 5)
 
 
 def fft_block_workspace(B, T, Cin, Cout, k, which):
     """Bytes for B utterances of at most T frames: ``which`` 0 a convolution (none), 1 its weight gradient (the transposed
     gradient slab and the slices' partial sums), 2 the column sums over Cout channels."""
-    n = C.c_longlong(0)
-    _check(load().t2amd_fft_block_workspace(int(B), int(T), int(Cin), int(Cout), int(k), int(which), C.byref(n)),
-           "t2amd_fft_block_workspace")
-    return n.value
-
-
-def _ffb_rows(who, x, name, shape):
-    if x is not None and (tuple(x.shape) != tuple(shape) or not x.is_contiguous()):
-        raise NativeError("%s: expected contiguous %s %s, got shape %s stride %s" % (who, name, tuple(shape), tuple(x.shape), x.stride()))
-    return ptr(x)
-
-
-def _ffb_x(who, x):
-    """(pointer, batch stride, frame stride) of a (B, T, C) float32 tensor with unit stride along C."""
-    if x.dim() != 3 or min(x.shape) < 1 or x.stride(2) != 1:
-        raise NativeError("%s: expected x (B, T, C) with unit stride along C, got shape %s stride %s" % (who, tuple(x.shape), x.stride()))
-    return [ptr(x)] + [_i64(x.stride(i) if x.shape[i] > 1 else 0) for i in range(2)]
+    return _query_bytes("t2amd_fft_block_workspace", int(B), int(T), int(Cin), int(Cout), int(k), int(which))
 
 
 def ffb_conv(x, image, bias, mask, lengths, k, relu, y):
@@ -2354,12 +2338,12 @@ def ffb_conv(x, image, bias, mask, lengths, k, relu, y):
     ``image`` (Cout, k Cin), every utterance alone over its own ``lengths[b]`` frames (device int32, clamped; None: T), +0 at and
     beyond them; ``bias`` (Cout) or None, ``relu``, and ``mask`` (B, T, Cout) or None: y is kept only where mask > 0."""
     who = "ffb_conv"
-    ax = _ffb_x(who, x)
+    ax = _operand(who, x, "x", "(B, T, C)")
     B, T, Cin = x.shape
     Cout = y.shape[2] if y.dim() == 3 else -1
-    _check(load().t2amd_ffb_conv_f32(*(ax + [_ffb_rows(who, image, "the weight image", (Cout, k * Cin)), _ffb_rows(who, bias, "bias", (Cout,)),
-                                              _ffb_rows(who, mask, "mask", (B, T, Cout)), _pair_lengths(who, lengths, B), B, T, Cin, Cout,
-                                              int(k), int(bool(relu)), _ffb_rows(who, y, "y", (B, T, Cout)), _stream()])),
+    _check(load().t2amd_ffb_conv_f32(*(ax + [_exact(who, image, "the weight image", (Cout, k * Cin)), _exact(who, bias, "bias", (Cout,)),
+                                              _exact(who, mask, "mask", (B, T, Cout)), _pair_lengths(who, lengths, B), B, T, Cin, Cout,
+                                              int(k), int(bool(relu)), _exact(who, y, "y", (B, T, Cout)), _stream()])),
            "t2amd_ffb_conv_f32")
 
 
@@ -2367,63 +2351,61 @@ def ffb_conv_dw(g, x, lengths, k, dw, ws):
     """dw (Cout, Cin, k) contiguous = sum over b then t of g(b, t, o) x(b, t + j - k // 2, i); g (B, T, Cout) contiguous, ``ws`` a
     uint8 tensor of at least ``fft_block_workspace(B, T, Cin, Cout, k, 1)`` bytes."""
     who = "ffb_conv_dw"
-    ax = _ffb_x(who, x)
+    ax = _operand(who, x, "x", "(B, T, C)")
     B, T, Cin = x.shape
     Cout = g.shape[2] if g.dim() == 3 else -1
-    pw, nw = _forward_sum_ws(who, ws)
-    _check(load().t2amd_ffb_conv_dw_f32(*([_ffb_rows(who, g, "g", (B, T, Cout))] + ax
+    pw, nw = _workspace(who, ws)
+    _check(load().t2amd_ffb_conv_dw_f32(*([_exact(who, g, "g", (B, T, Cout))] + ax
                                           + [_pair_lengths(who, lengths, B), B, T, Cin, Cout, int(k),
-                                             _ffb_rows(who, dw, "dw", (Cout, Cin, k)), pw, nw, _stream()])), "t2amd_ffb_conv_dw_f32")
+                                             _exact(who, dw, "dw", (Cout, Cin, k)), pw, nw, _stream()])), "t2amd_ffb_conv_dw_f32")
+
+
+def _ffb_shape(who, x, name):
+    if x.dim() != 3:
+        raise NativeError("%s: expected %s (B, T, C), got %s" % (who, name, tuple(x.shape)))
+    return x.shape
 
 
 def ffb_add_ln(x, residual, weight, bias, lengths, eps, y, z=None, mean=None, rstd=None):
     """y = LayerNorm(x + residual) weight + bias over the last axis of (B, T, C) on the rows below ``lengths``, +0 beyond;
     ``weight`` None: y = x + residual ("add and mask").  ``z`` (B, T, C), ``mean`` and ``rstd`` (B, T) are kept where given."""
     who = "ffb_add_ln"
-    if x.dim() != 3:
-        raise NativeError("%s: expected x (B, T, C), got %s" % (who, tuple(x.shape)))
-    B, T, C_ = x.shape
-    _check(load().t2amd_ffb_add_ln_f32(_ffb_rows(who, x, "x", x.shape), _ffb_rows(who, residual, "residual", x.shape),
-                                       _ffb_rows(who, weight, "weight", (C_,)), _ffb_rows(who, bias, "bias", (C_,)),
-                                       _pair_lengths(who, lengths, B), B, T, C_, float(eps), _ffb_rows(who, y, "y", x.shape),
-                                       _ffb_rows(who, z, "z", x.shape), _ffb_rows(who, mean, "mean", (B, T)),
-                                       _ffb_rows(who, rstd, "rstd", (B, T)), _stream()), "t2amd_ffb_add_ln_f32")
+    B, T, C_ = _ffb_shape(who, x, "x")
+    _check(load().t2amd_ffb_add_ln_f32(_exact(who, x, "x", x.shape), _exact(who, residual, "residual", x.shape),
+                                       _exact(who, weight, "weight", (C_,)), _exact(who, bias, "bias", (C_,)),
+                                       _pair_lengths(who, lengths, B), B, T, C_, float(eps), _exact(who, y, "y", x.shape),
+                                       _exact(who, z, "z", x.shape), _exact(who, mean, "mean", (B, T)),
+                                       _exact(who, rstd, "rstd", (B, T)), _stream()), "t2amd_ffb_add_ln_f32")
 
 
 def ffb_add_ln_backward(g, z, mean, rstd, weight, lengths, dz):
     """dz (B, T, C) = the LayerNorm input gradient of g from the kept z, mean and rstd."""
     who = "ffb_add_ln_backward"
-    if z.dim() != 3:
-        raise NativeError("%s: expected z (B, T, C), got %s" % (who, tuple(z.shape)))
-    B, T, C_ = z.shape
-    _check(load().t2amd_ffb_add_ln_bwd_f32(_ffb_rows(who, g, "g", z.shape), _ffb_rows(who, z, "z", z.shape),
-                                           _ffb_rows(who, mean, "mean", (B, T)), _ffb_rows(who, rstd, "rstd", (B, T)),
-                                           _ffb_rows(who, weight, "weight", (C_,)), _pair_lengths(who, lengths, B), B, T, C_,
-                                           _ffb_rows(who, dz, "dz", z.shape), _stream()), "t2amd_ffb_add_ln_bwd_f32")
+    B, T, C_ = _ffb_shape(who, z, "z")
+    _check(load().t2amd_ffb_add_ln_bwd_f32(_exact(who, g, "g", z.shape), _exact(who, z, "z", z.shape),
+                                           _exact(who, mean, "mean", (B, T)), _exact(who, rstd, "rstd", (B, T)),
+                                           _exact(who, weight, "weight", (C_,)), _pair_lengths(who, lengths, B), B, T, C_,
+                                           _exact(who, dz, "dz", z.shape), _stream()), "t2amd_ffb_add_ln_bwd_f32")
 
 
 def ffb_colsum(g, z, mean, rstd, lengths, dbias, dweight, ws):
     """dbias (C) = the column sums of g (B, T, C) over the real rows and, with z, mean and rstd, dweight (C) = those of
     g (z - mean) rstd; ``ws`` a uint8 tensor of at least ``fft_block_workspace(B, T, C, C, 1, 2)`` bytes."""
     who = "ffb_colsum"
-    if g.dim() != 3:
-        raise NativeError("%s: expected g (B, T, C), got %s" % (who, tuple(g.shape)))
-    B, T, C_ = g.shape
-    pw, nw = _forward_sum_ws(who, ws)
-    _check(load().t2amd_ffb_colsum_f32(_ffb_rows(who, g, "g", g.shape), _ffb_rows(who, z, "z", g.shape), _ffb_rows(who, mean, "mean", (B, T)),
-                                       _ffb_rows(who, rstd, "rstd", (B, T)), _pair_lengths(who, lengths, B), B, T, C_,
-                                       _ffb_rows(who, dbias, "dbias", (C_,)), _ffb_rows(who, dweight, "dweight", (C_,)), pw, nw, _stream()),
+    B, T, C_ = _ffb_shape(who, g, "g")
+    pw, nw = _workspace(who, ws)
+    _check(load().t2amd_ffb_colsum_f32(_exact(who, g, "g", g.shape), _exact(who, z, "z", g.shape), _exact(who, mean, "mean", (B, T)),
+                                       _exact(who, rstd, "rstd", (B, T)), _pair_lengths(who, lengths, B), B, T, C_,
+                                       _exact(who, dbias, "dbias", (C_,)), _exact(who, dweight, "dweight", (C_,)), pw, nw, _stream()),
            "t2amd_ffb_colsum_f32")
 
 
 def ffb_relu_mask(g, y, lengths, out):
     """out = g where y > 0 and +0 elsewhere and beyond ``lengths``: the gradient below a ReLU; all (B, T, C) contiguous."""
     who = "ffb_relu_mask"
-    if g.dim() != 3:
-        raise NativeError("%s: expected g (B, T, C), got %s" % (who, tuple(g.shape)))
-    B, T, C_ = g.shape
-    _check(load().t2amd_ffb_relu_mask_f32(_ffb_rows(who, g, "g", g.shape), _ffb_rows(who, y, "y", g.shape), _pair_lengths(who, lengths, B),
-                                          B, T, C_, _ffb_rows(who, out, "out", g.shape), _stream()), "t2amd_ffb_relu_mask_f32")
+    B, T, C_ = _ffb_shape(who, g, "g")
+    _check(load().t2amd_ffb_relu_mask_f32(_exact(who, g, "g", g.shape), _exact(who, y, "y", g.shape), _pair_lengths(who, lengths, B),
+                                          B, T, C_, _exact(who, out, "out", g.shape), _stream()), "t2amd_ffb_relu_mask_f32")
 
 
 # ----------------------------------------------------------------------------

@@ -22,7 +22,7 @@ import math
 import torch
 
 from . import native as nv
-from .audio import _lengths
+from . import ragged as rg
 
 MAX_FRAMES = 4096
 MAX_HEADS = 16
@@ -31,21 +31,12 @@ MAX_HEAD_WIDTH = 128
 MAX_BATCH_HEADS = 65535
 
 
-def _as_operand(x):
-    """``x`` (B, T, H, D) as the kernels take it: unit stride along D, the other strides positive multiples of 4 floats, the base
-    on 16 bytes.  The chunks of a packed (B, T, 3 H D) projection pass as they are; anything else is copied."""
-    ok = x.stride(3) == 1 and all(x.shape[i] == 1 or (x.stride(i) > 0 and x.stride(i) % 4 == 0) for i in range(3))
-    if not ok:
-        x = x.contiguous()
-    return x if x.data_ptr() % 16 == 0 else x.clone(memory_format=torch.contiguous_format)
-
-
 class _SelfAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, len_dev, scale, keep):
         B, T, H, D = q.shape
         dev = q.device
-        qd, kd, vd = (_as_operand(t.detach()) for t in (q, k, v))
+        qd, kd, vd = (rg.aligned(t.detach()) for t in (q, k, v))     # the chunks of a packed projection pass as they are
         o = torch.empty(B, T, H, D, dtype=torch.float32, device=dev)
         lse = torch.empty(B, H, T, dtype=torch.float32, device=dev) if keep else None
         nv.self_attn(qd, kd, vd, len_dev, scale, o, lse)
@@ -60,29 +51,11 @@ class _SelfAttention(torch.autograd.Function):
         q, k, v, o, lse = ctx.saved_tensors[:5]
         len_dev = ctx.saved_tensors[5] if ctx.has_len else None
         B, T, H, D = q.shape
-        g = _as_operand(grad.float())
+        g = rg.aligned(grad.float())
         dq, dk, dv = (torch.empty(B, T, H, D, dtype=torch.float32, device=q.device) for _ in range(3))
-        ws = torch.empty(nv.self_attn_workspace(B, T, H, D, 2), dtype=torch.uint8, device=q.device)
+        ws = rg.workspace(nv.self_attn_workspace(B, T, H, D, 2), q.device)
         nv.self_attn_backward(q, k, v, o, lse, g, len_dev, ctx.scale, dq, dk, dv, ws)
         return dq, dk, dv, None, None, None
-
-
-def _attention_lengths(who, lengths, B, T, dev, what="q"):
-    """The frame counts as a device int32 vector, or None.  A host list is checked against [0, T] and uploaded; a device tensor is
-    not read here: the kernels clamp it."""
-    if lengths is None:
-        return None
-    if torch.is_tensor(lengths) and lengths.device.type != "cpu":
-        if lengths.device != dev:
-            raise ValueError("%s: %s is on %s and lengths on %s" % (who, what, dev, lengths.device))
-        if lengths.dim() != 1 or lengths.numel() != B or lengths.is_floating_point():
-            raise ValueError("%s: expected %d integer lengths, got shape %s %s" % (who, B, tuple(lengths.shape), lengths.dtype))
-        return lengths.detach().to(torch.int32).contiguous()
-    ln = _lengths(lengths, B, None, who + ": ")
-    for b in range(B):
-        if not 0 <= ln[b] <= T:
-            raise ValueError("%s: utterance %d: %d frames do not lie in [0, %d]" % (who, b, ln[b], T))
-    return torch.tensor(ln, dtype=torch.int32).to(dev)
 
 
 def self_attention(q, k, v, lengths=None, scale=None):
@@ -100,8 +73,7 @@ def self_attention(q, k, v, lengths=None, scale=None):
     otherwise q, k, v, o and a (B, H, T) logsumexp are kept."""
     who = "self_attention"
     for name, t in (("q", q), ("k", k), ("v", v)):
-        if not torch.is_tensor(t) or t.dtype != torch.float32:
-            raise TypeError("%s: expected float32 %s, got %s" % (who, name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+        rg.float32(who, t, name)
     if q.dim() == 3 and k.dim() == 3 and v.dim() == 3:
         q, k, v = q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0)
     if q.dim() != 4 or min(q.shape) < 1 or k.shape != q.shape or v.shape != q.shape:
@@ -118,16 +90,14 @@ def self_attention(q, k, v, lengths=None, scale=None):
         raise ValueError("%s: %d utterances times %d heads exceed the limit of %d" % (who, B, H, MAX_BATCH_HEADS))
     if scale is None:
         scale = 1.0 / math.sqrt(D)
-    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not 0.0 < float(scale) < float("inf"):
-        raise ValueError("%s: the scale must be a positive number, got %r" % (who, scale))
+    scale = rg.positive(who, scale, "the scale must be a positive number", bools=False)
     for name, t in (("k", k), ("v", v)):
         if t.device != q.device:
             raise ValueError("%s: q is on %s and %s on %s" % (who, q.device, name, t.device))
-    if not q.is_cuda and not nv.validate_only():
-        raise nv.NativeError("%s: q, k and v are on %s; move them to the MI355X first, there is no CPU path" % (who, q.device))
-    len_dev = _attention_lengths(who, lengths, B, T, q.device)
+    rg.require_device(q, who, "q, k and v are")
+    len_dev = rg.device_lengths(who, lengths, B, T, q.device, "q is")
     keep = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))
-    return _SelfAttention.apply(q, k, v, len_dev, float(scale), keep)
+    return _SelfAttention.apply(q, k, v, len_dev, scale, keep)
 
 
 class MultiHeadSelfAttention(torch.nn.Module):
@@ -177,23 +147,14 @@ MIN_NORM_CHANNELS = 32
 MAX_BATCH = 65535
 
 
-def _as_rows(x):
-    """``x`` (B, T, C) as the convolution reads it: unit stride along C, the other strides positive multiples of 4 floats, the
-    base on 16 bytes; anything else is copied."""
-    ok = x.stride(2) == 1 and all(x.shape[i] == 1 or (x.stride(i) > 0 and x.stride(i) % 4 == 0) for i in range(2))
-    if not ok:
-        x = x.contiguous()
-    return x if x.data_ptr() % 16 == 0 else x.clone(memory_format=torch.contiguous_format)
-
-
 def _dense(x):
     """``x`` contiguous float32 on 16 bytes."""
-    x = x.float().contiguous()
-    return x if x.data_ptr() % 16 == 0 else x.clone(memory_format=torch.contiguous_format)
+    return rg.aligned(x.float(), strided=False)
 
 
-def _workspace(nbytes, dev):
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+def _workspace(dev, *geometry):
+    """The workspace ``native.fft_block_workspace`` asks for, of 16 bytes at least."""
+    return rg.workspace(nv.fft_block_workspace(*geometry), dev, least=16)
 
 
 class _RaggedConv1d(torch.autograd.Function):
@@ -201,7 +162,7 @@ class _RaggedConv1d(torch.autograd.Function):
     def forward(ctx, x, weight, bias, len_dev, relu, keep):
         B, T, Cin = x.shape
         Cout, _, k = weight.shape
-        xd, wd = _as_rows(x.detach()), weight.detach()
+        xd, wd = rg.aligned(x.detach()), weight.detach()
         image = _dense(wd.permute(0, 2, 1).reshape(Cout, k * Cin))          # [o][j Cin + i]: a torch permute, once a call
         y = torch.empty(B, T, Cout, dtype=torch.float32, device=x.device)
         nv.ffb_conv(xd, image, None if bias is None else _dense(bias.detach()), None, len_dev, k, relu, y)
@@ -232,10 +193,10 @@ class _RaggedConv1d(torch.autograd.Function):
             nv.ffb_conv(g, image, None, None, len_dev, k, False, dx)
         if ctx.needs_input_grad[1]:
             dw = torch.empty(Cout, Cin, k, dtype=torch.float32, device=dev)
-            nv.ffb_conv_dw(g, x, len_dev, k, dw, _workspace(nv.fft_block_workspace(B, T, Cin, Cout, k, 1), dev))
+            nv.ffb_conv_dw(g, x, len_dev, k, dw, _workspace(dev, B, T, Cin, Cout, k, 1))
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = torch.empty(Cout, dtype=torch.float32, device=dev)
-            nv.ffb_colsum(g, None, None, None, len_dev, db, None, _workspace(nv.fft_block_workspace(B, T, Cout, Cout, 1, 2), dev))
+            nv.ffb_colsum(g, None, None, None, len_dev, db, None, _workspace(dev, B, T, Cout, Cout, 1, 2))
         return dx, dw, db, None, None, None
 
 
@@ -275,13 +236,12 @@ class _AddLayerNorm(torch.autograd.Function):
             nv.ffb_add_ln_backward(g, z, mean, rstd, w, len_dev, dz)
             if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
                 dw, db = (torch.empty(C, dtype=torch.float32, device=g.device) for _ in range(2))
-                nv.ffb_colsum(g, z, mean, rstd, len_dev, db, dw, _workspace(nv.fft_block_workspace(B, T, C, C, 1, 2), g.device))
+                nv.ffb_colsum(g, z, mean, rstd, len_dev, db, dw, _workspace(g.device, B, T, C, C, 1, 2))
         return dz, (dz if ctx.has_res else None), dw, db, None, None, None
 
 
 def _check_rows(who, x, name="x"):
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise TypeError("%s: expected float32 %s, got %s" % (who, name, x.dtype if torch.is_tensor(x) else type(x).__name__))
+    rg.float32(who, x, name)
     if x.dim() != 3 or min(x.shape) < 1:
         raise ValueError("%s: expected %s (B, T, C), got %s" % (who, name, tuple(x.shape)))
     if x.shape[1] > MAX_FRAMES:
@@ -291,8 +251,7 @@ def _check_rows(who, x, name="x"):
 
 
 def _check_param(who, p, name, shape, dev):
-    if not torch.is_tensor(p) or p.dtype != torch.float32:
-        raise TypeError("%s: expected float32 %s, got %s" % (who, name, p.dtype if torch.is_tensor(p) else type(p).__name__))
+    rg.float32(who, p, name)
     if tuple(p.shape) != tuple(shape):
         raise ValueError("%s: expected %s %s, got %s" % (who, name, tuple(shape), tuple(p.shape)))
     if p.device != dev:
@@ -315,8 +274,7 @@ def ragged_conv1d(x, weight, bias=None, lengths=None, relu=False):
     under ``no_grad`` nothing is."""
     who = "ragged_conv1d"
     _check_rows(who, x)
-    if not torch.is_tensor(weight) or weight.dtype != torch.float32:
-        raise TypeError("%s: expected float32 weight, got %s" % (who, weight.dtype if torch.is_tensor(weight) else type(weight).__name__))
+    rg.float32(who, weight, "weight")
     B, T, Cin = x.shape
     if weight.dim() != 3 or weight.shape[1] != Cin:
         raise ValueError("%s: expected weight (Cout, %d, k), got %s" % (who, Cin, tuple(weight.shape)))
@@ -330,9 +288,8 @@ def ragged_conv1d(x, weight, bias=None, lengths=None, relu=False):
         raise ValueError("%s: x is on %s and weight on %s" % (who, x.device, weight.device))
     if bias is not None:
         _check_param(who, bias, "bias", (Cout,), x.device)
-    if not x.is_cuda and not nv.validate_only():
-        raise nv.NativeError("%s: x is on %s; move it to the MI355X first, there is no CPU path" % (who, x.device))
-    len_dev = _attention_lengths(who, lengths, B, T, x.device, "x")
+    rg.require_device(x, who, "x is")
+    len_dev = rg.device_lengths(who, lengths, B, T, x.device, "x is")
     keep = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias))
     return _RaggedConv1d.apply(x, weight, bias, len_dev, bool(relu), keep)
 
@@ -356,13 +313,11 @@ def add_layer_norm(x, residual=None, weight=None, bias=None, lengths=None, eps=1
     if weight is not None:
         _check_param(who, weight, "weight", (C,), x.device)
         _check_param(who, bias, "bias", (C,), x.device)
-    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 < float(eps) < float("inf"):
-        raise ValueError("%s: eps must be a positive number, got %r" % (who, eps))
-    if not x.is_cuda and not nv.validate_only():
-        raise nv.NativeError("%s: x is on %s; move it to the MI355X first, there is no CPU path" % (who, x.device))
-    len_dev = _attention_lengths(who, lengths, B, T, x.device, "x")
+    eps = rg.positive(who, eps, "eps must be a positive number", bools=False)
+    rg.require_device(x, who, "x is")
+    len_dev = rg.device_lengths(who, lengths, B, T, x.device, "x is")
     keep = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, residual, weight, bias))
-    return _AddLayerNorm.apply(x, residual, weight, bias, len_dev, float(eps), keep)
+    return _AddLayerNorm.apply(x, residual, weight, bias, len_dev, eps, keep)
 
 
 class PositionwiseConvFF(torch.nn.Module):
@@ -393,7 +348,7 @@ class PositionwiseConvFF(torch.nn.Module):
                              % (self.d_model, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
         ln = self.layer_norm
         if lengths is not None:
-            lengths = _attention_lengths("PositionwiseConvFF", lengths, x.shape[0], x.shape[1], x.device, "x")
+            lengths = rg.device_lengths("PositionwiseConvFF", lengths, x.shape[0], x.shape[1], x.device, "x is")
         h = add_layer_norm(x, None, ln.weight, ln.bias, lengths, ln.eps) if self.pre_lnorm else x
         h = ragged_conv1d(h, self.conv1.weight, self.conv1.bias, lengths, relu=True)
         h = ragged_conv1d(h, self.conv2.weight, self.conv2.bias, lengths)
@@ -413,7 +368,7 @@ class FFTBlock(torch.nn.Module):
 
     def forward(self, x, lengths=None):
         if lengths is not None and torch.is_tensor(x) and x.dim() == 3:
-            lengths = _attention_lengths("FFTBlock", lengths, x.shape[0], x.shape[1], x.device, "x")
+            lengths = rg.device_lengths("FFTBlock", lengths, x.shape[0], x.shape[1], x.device, "x is")
         return self.pos_ff(self.dec_attn(x, lengths), lengths)
 
 
@@ -458,7 +413,7 @@ class FFTransformer(torch.nn.Module):
             raise ValueError("FFTransformer: expected x (B, T, %d), got %s"
                              % (self.d_model, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
         B, T, _ = x.shape
-        len_dev = _attention_lengths("FFTransformer", lengths, B, T, x.device, "x")
+        len_dev = rg.device_lengths("FFTransformer", lengths, B, T, x.device, "x is")
         out = x + positional_embedding(T, self.d_model, None if len_dev is None else len_dev.clamp(0, T), x.device)
         for layer in self.layers:
             out = layer(out, len_dev)
