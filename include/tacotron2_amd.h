@@ -1195,6 +1195,43 @@ int t2amd_ffb_colsum_f32(const float* g, const float* z, const float* mean, cons
 /* out = g where y > 0 and +0 elsewhere: the gradient below a ReLU. */
 int t2amd_ffb_relu_mask_f32(const float* g, const float* y, const int* lengths, int B, int T, int C, float* out, void* stream);
 
+/* The thin ends of a temporal predictor (csrc/predictor_rows.hip), which the ragged convolution above
+ * cannot express: the projection of C channels onto P values per row and the embedding of P scalar tracks into C channels with k
+ * taps, over a ragged batch as above (lengths: device int32, clamped into [0, T]; NULL: T).  Float32, contiguous, channel-last:
+ * h, base, y of the embedding, g of the embedding (B, T, C) on 16 bytes; the tracks v and the projection's y and g (B, T, P).
+ * 1 <= P <= 4; k odd, at most 9; C a multiple of 4 from 32 to 4096; T <= 4096; B <= 65535.  Rows at and beyond T_b are never read
+ * and every output is +0 there.  Row kernels: one wave per row, no atomics, one writer per element, every sum in a fixed order.
+ * Error texts begin with "predictor:". */
+/* *max_frames = 4096, *max_channels = 4096, *max_taps = 9, *max_tracks = 4, *max_batch = 65535. */
+int t2amd_predictor_limits(int* max_frames, int* max_channels, int* max_taps, int* max_tracks, int* max_batch);
+/* which 0: the forwards and the input gradients (none: 0 bytes); 1: t2amd_pred_project_sums_f32 (k is checked, not used); 2:
+ * t2amd_pred_embed_sums_f32. */
+int t2amd_predictor_workspace(int B, int T, int C, int P, int k, int which, long long* bytes);
+/* y(b, t, p) = bias(p) + sum_c w(p, c) h(b, t, c) for t < T_b: lane l of 64 chains fmaf over the components of the float4 chunks
+ * l, l + 64, .. from +0, the xor butterfly 32 .. 1, then the bias.  w is [P][C]; bias [P] or NULL. */
+int t2amd_pred_project_f32(const float* h, const float* w, const float* bias, const int* lengths, int B, int T, int C, int P, float* y,
+                           void* stream);
+/* dh(b, t, c) = sum_p g(b, t, p) w(p, c), an fmaf chain over p ascending from +0. */
+int t2amd_pred_project_bwd_f32(const float* g, const float* w, const int* lengths, int B, int T, int C, int P, float* dh, void* stream);
+/* dw(p, c) = sum of g(b, t, p) h(b, t, c) (fmaf) and db(p) = sum of g(b, t, p) (adds) over the real rows: partial sums over runs of
+ * the flattened (b, t) ascending, then the partials ascending from +0.  dw or db may be NULL, not both. */
+int t2amd_pred_project_sums_f32(const float* g, const float* h, const int* lengths, int B, int T, int C, int P, float* dw, float* db,
+                                unsigned char* ws, long long ws_bytes, void* stream);
+/* y(b, t, c) = base(b, t, c) + (bias(c) + sum_{p, j} image[p k + j][c] v(b, t + j - k/2, p)) for t < T_b over the frames inside
+ * [0, T_b) only: an fmaf chain over p then j ascending from +0, then the bias, then the base.  image is [P k][C] with
+ * image[p k + j][c] = w(c, p, j); bias [C] or NULL; base (B, T, C) or NULL. */
+int t2amd_pred_embed_f32(const float* v, const float* image, const float* bias, const float* base, const int* lengths, int B, int T,
+                         int C, int P, int k, float* y, void* stream);
+/* dbase (B, T, C) = g masked to the real rows; dv(b, t, p) = sum over j ascending of u(b, t - j + k/2, p, j) over the rows inside
+ * the utterance, u(b, t, p, j) = sum_c image[p k + j][c] g(b, t, c) in the order of t2amd_pred_project_f32.  dbase or dv may be
+ * NULL, not both; image may be NULL without dv. */
+int t2amd_pred_embed_bwd_f32(const float* g, const float* image, const int* lengths, int B, int T, int C, int P, int k, float* dbase,
+                             float* dv, void* stream);
+/* dw (C, P, k) = sum of g(b, t, c) v(b, t + j - k/2, p) (fmaf) and db(c) = sum of g(b, t, c) (adds) over the real rows, by the
+ * partial sums of t2amd_pred_project_sums_f32.  dw or db may be NULL, not both. */
+int t2amd_pred_embed_sums_f32(const float* g, const float* v, const int* lengths, int B, int T, int C, int P, int k, float* dw,
+                              float* db, unsigned char* ws, long long ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Griffin-Lim vocoder (csrc/vocoder.hip): element passes around the two GEMMs of one
  * Griffin-Lim iteration (reference audio_processing.py:59-76, stft.py:77-141).  The contractions are

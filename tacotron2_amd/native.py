@@ -303,6 +303,8 @@ SYMBOLS = [
     "t2amd_self_attn_bwd_f32",
     "t2amd_fft_block_limits", "t2amd_fft_block_workspace", "t2amd_ffb_conv_f32", "t2amd_ffb_conv_dw_f32", "t2amd_ffb_transpose_f32",
     "t2amd_ffb_dw_finish_f32", "t2amd_ffb_add_ln_f32", "t2amd_ffb_add_ln_bwd_f32", "t2amd_ffb_colsum_f32", "t2amd_ffb_relu_mask_f32",
+    "t2amd_predictor_limits", "t2amd_predictor_workspace", "t2amd_pred_project_f32", "t2amd_pred_project_bwd_f32",
+    "t2amd_pred_project_sums_f32", "t2amd_pred_embed_f32", "t2amd_pred_embed_bwd_f32", "t2amd_pred_embed_sums_f32",
     "t2amd_gl_packed_rows", "t2amd_gl_overlap_add_f32", "t2amd_gl_project_f32", "t2amd_gl_rect_f32", "t2amd_stft_polar_f32",
     "t2amd_mel_decompress_f32",
     "t2amd_wg_layer_f32", "t2amd_wg_tail_f32", "t2amd_wg_denoise_f32", "t2amd_wg_head_f32", "t2amd_wg_nll_chunk", "t2amd_wg_nll_f32",
@@ -463,6 +465,14 @@ def _argtypes():
         "t2amd_ffb_add_ln_bwd_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
         "t2amd_ffb_colsum_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
         "t2amd_ffb_relu_mask_f32": [_P, _P, _P, _I, _I, _I, _P, _P],
+        "t2amd_predictor_limits": [pt(C.c_int)] * 5,
+        "t2amd_predictor_workspace": [_I, _I, _I, _I, _I, _I, pt(C.c_longlong)],
+        "t2amd_pred_project_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+        "t2amd_pred_project_bwd_f32": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
+        "t2amd_pred_project_sums_f32": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+        "t2amd_pred_embed_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+        "t2amd_pred_embed_bwd_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+        "t2amd_pred_embed_sums_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
         "t2amd_gl_overlap_add_f32": [_P, _L, _P, _P, _P, _I, _L, _I, _I, _F, _P, _L, _L, _I, _P],
         "t2amd_gl_project_f32": [_P, _L, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P],
         "t2amd_gl_rect_f32": [_P, _P, _L, _P, _P, _I, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
@@ -2406,6 +2416,90 @@ def ffb_relu_mask(g, y, lengths, out):
     B, T, C_ = _ffb_shape(who, g, "g")
     _check(load().t2amd_ffb_relu_mask_f32(_exact(who, g, "g", g.shape), _exact(who, y, "y", g.shape), _pair_lengths(who, lengths, B),
                                           B, T, C_, _exact(who, out, "out", g.shape), _stream()), "t2amd_ffb_relu_mask_f32")
+
+
+# ---- the thin ends of a temporal predictor: channel projection and scalar embedding (csrc/predictor_rows.hip) --------------------
+def predictor_limits():
+    """-> (frames at most, channels at most, kernel width at most, scalar tracks at most, utterances at most)."""
+    return _query_ints("t2amd_predictor_limits", 5)
+
+
+def predictor_workspace(B, T, C_, P, k, which):
+    """Bytes for B utterances of at most T frames, C channels, P tracks and k taps: ``which`` 0 the forwards and the input
+    gradients (none), 1 the projection's dw and db, 2 the embedding's."""
+    return _query_bytes("t2amd_predictor_workspace", int(B), int(T), int(C_), int(P), int(k), int(which))
+
+
+def _pred_shape(who, x, name, axes="(B, T, C)"):
+    if x.dim() != 3:
+        raise NativeError("%s: expected %s %s, got %s" % (who, name, axes, tuple(x.shape)))
+    return x.shape
+
+
+def pred_project(h, w, bias, lengths, y):
+    """y (B, T, P) = bias + h w^T on the rows below ``lengths`` (device int32, clamped; None: T), +0 beyond; h (B, T, C), w (P, C),
+    ``bias`` (P) or None; all contiguous."""
+    who = "pred_project"
+    B, T, C_ = _pred_shape(who, h, "h")
+    P = w.shape[0] if w.dim() == 2 else -1
+    _check(load().t2amd_pred_project_f32(_exact(who, h, "h", h.shape), _exact(who, w, "w", (P, C_)), _exact(who, bias, "bias", (P,)),
+                                         _pair_lengths(who, lengths, B), B, T, C_, P, _exact(who, y, "y", (B, T, P)), _stream()),
+           "t2amd_pred_project_f32")
+
+
+def pred_project_backward(g, w, lengths, dh):
+    """dh (B, T, C) = g w on the rows below ``lengths``, +0 beyond; g (B, T, P), w (P, C)."""
+    who = "pred_project_backward"
+    B, T, C_ = _pred_shape(who, dh, "dh")
+    P = w.shape[0] if w.dim() == 2 else -1
+    _check(load().t2amd_pred_project_bwd_f32(_exact(who, g, "g", (B, T, P)), _exact(who, w, "w", (P, C_)), _pair_lengths(who, lengths, B),
+                                             B, T, C_, P, _exact(who, dh, "dh", dh.shape), _stream()), "t2amd_pred_project_bwd_f32")
+
+
+def pred_project_sums(g, h, lengths, dw, db, ws):
+    """dw (P, C) = the sum of g(b, t, p) h(b, t, c) and db (P) = the sum of g over the real rows (either may be None); ``ws`` a uint8
+    tensor of at least ``predictor_workspace(B, T, C, P, 1, 1)`` bytes."""
+    who = "pred_project_sums"
+    B, T, C_ = _pred_shape(who, h, "h")
+    P = g.shape[2] if g.dim() == 3 else -1
+    pw, nw = _workspace(who, ws)
+    _check(load().t2amd_pred_project_sums_f32(_exact(who, g, "g", (B, T, P)), _exact(who, h, "h", h.shape), _pair_lengths(who, lengths, B),
+                                              B, T, C_, P, _exact(who, dw, "dw", (P, C_)), _exact(who, db, "db", (P,)), pw, nw, _stream()),
+           "t2amd_pred_project_sums_f32")
+
+
+def pred_embed(v, image, bias, base, lengths, k, y):
+    """y (B, T, C) = base + (bias + the k-tap embedding of the tracks v (B, T, P) under ``image`` (P k, C)), every utterance alone over
+    its own ``lengths[b]`` frames, +0 at and beyond them; ``bias`` (C) and ``base`` (B, T, C) may be None."""
+    who = "pred_embed"
+    B, T, C_ = _pred_shape(who, y, "y")
+    P = v.shape[2] if v.dim() == 3 else -1
+    _check(load().t2amd_pred_embed_f32(_exact(who, v, "v", (B, T, P)), _exact(who, image, "the weight image", (P * int(k), C_)),
+                                       _exact(who, bias, "bias", (C_,)), _exact(who, base, "base", y.shape),
+                                       _pair_lengths(who, lengths, B), B, T, C_, P, int(k), _exact(who, y, "y", y.shape), _stream()),
+           "t2amd_pred_embed_f32")
+
+
+def pred_embed_backward(g, image, lengths, P, k, dbase, dv):
+    """dbase (B, T, C) = g on the real rows and +0 beyond; dv (B, T, P) = the gradient of the tracks under ``image`` (P k, C);
+    either may be None (``image`` too without dv)."""
+    who = "pred_embed_backward"
+    B, T, C_ = _pred_shape(who, g, "g")
+    _check(load().t2amd_pred_embed_bwd_f32(_exact(who, g, "g", g.shape), _exact(who, image, "the weight image", (int(P) * int(k), C_)),
+                                           _pair_lengths(who, lengths, B), B, T, C_, int(P), int(k), _exact(who, dbase, "dbase", g.shape),
+                                           _exact(who, dv, "dv", (B, T, int(P))), _stream()), "t2amd_pred_embed_bwd_f32")
+
+
+def pred_embed_sums(g, v, lengths, k, dw, db, ws):
+    """dw (C, P, k) = the sum of g(b, t, c) v(b, t + j - k // 2, p) and db (C) = the sum of g over the real rows (either may be None);
+    ``ws`` a uint8 tensor of at least ``predictor_workspace(B, T, C, P, k, 2)`` bytes."""
+    who = "pred_embed_sums"
+    B, T, C_ = _pred_shape(who, g, "g")
+    P = v.shape[2] if v.dim() == 3 else -1
+    pw, nw = _workspace(who, ws)
+    _check(load().t2amd_pred_embed_sums_f32(_exact(who, g, "g", g.shape), _exact(who, v, "v", (B, T, P)), _pair_lengths(who, lengths, B),
+                                            B, T, C_, P, int(k), _exact(who, dw, "dw", (C_, P, int(k))), _exact(who, db, "db", (C_,)),
+                                            pw, nw, _stream()), "t2amd_pred_embed_sums_f32")
 
 
 # ----------------------------------------------------------------------------
